@@ -12,7 +12,21 @@ Headline (every N) — config 2 of BASELINE.json: a 16 384 x 1 024 fp32 model
        (KeyRange.java:68-80); step = ordered pre-reduce of the 32 local pushes,
        RCCL reduce-scatter of the partials (pipelined in row slices), owner apply.
 
-Legs reported in the same JSON line (same N, same process group):
+A plain run (`python bench.py --gpus N --steps K --warmup W`) sets up, warms up,
+times exactly K steps of the headline and prints the line: metric, value, unit,
+higher_is_better, dtype, ms_per_step (one timed step, milliseconds), the config and
+the sampled-launch roofline of the timed steps. `--dump-outputs DIR` also writes
+what the timed steps computed (below). Everything that takes runs of its own — the
+arrival-order variants, the measured stream peaks, the legs below, the native
+group, the CPU baselines — runs only with `--full`.
+
+`--dump-outputs DIR`: the shard is refilled (synth_fill(7)) right before the timed
+region, so its state after the last timed step depends on the arguments alone;
+DIR/shard.npy holds a fixed seeded sample of its rows (float32, as a caller's
+values() / fetch returns them) and DIR/shard_row_sums.npy the float64 sum of every
+row (rank r of N > 1 writes shard_rank<r>*.npy).
+
+Legs reported in the same JSON line with `--full` (same N, same process group):
   "config4": BASELINE config 4, Word2Vec rows 10M x 200 fp32 (8 GB model),
              W full-range pushes per GPU ([int32][200 x f32] = 804 B records);
              N=1 one store, N>1 linearSplit + pre-reduce + reduce-scatter
@@ -192,6 +206,31 @@ def timed_steps(ctx: Ctx, step, finish, steps: int, warmup: int, ramp_s: float =
     finish()
     ctx.barrier()
     return ctx.max(time.perf_counter() - t0)
+
+
+# ---------------------------------------------------------------- --dump-outputs
+DUMP_SEED = 20240                        # the row sample of --dump-outputs
+DUMP_BYTES = 48_000_000                  # sampled rows written per run, all ranks together
+
+
+def dump_rows(n_rows: int, row_bytes: int, budget: int):
+    """The rows --dump-outputs writes: all of them if they fit `budget` bytes, else a
+    fixed seeded sample (ascending), the same for every run of the same shape."""
+    import numpy as np
+    k = max(1, min(n_rows, budget // row_bytes))
+    if k == n_rows:
+        return np.arange(n_rows)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=k, replace=False))
+
+
+def dump_outputs(dirname: str, name: str, values, budget: int = DUMP_BYTES) -> None:
+    """DIR/<name>.npy: the sampled rows of `values` (a 2-D float32 array) as they are;
+    DIR/<name>_row_sums.npy: every row's sum in float64 (covers the rows not sampled)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    rows = dump_rows(values.shape[0], values.shape[1] * values.itemsize, budget)
+    np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(values[rows], dtype=np.float32))
+    np.save(os.path.join(dirname, name + "_row_sums.npy"), values.sum(axis=1, dtype=np.float64))
 
 
 # ---------------------------------------------------------------- host / CPU baseline
@@ -420,7 +459,7 @@ def headline(ctx: Ctx, L, args, out_line: dict):
         # selector applies pushes in arrival order (PSAgent.java:166-186)
         import random
         shuffled_batches = []
-        for k in range(SHUFFLE_ORDERS):
+        for k in range(SHUFFLE_ORDERS if args.full else 0):
             bs = bufs[:W] if k % 2 == 0 else bufs[W:]
             order = list(range(W))
             # diagnostics: one order every step (--shuffle-orders 1), or only the
@@ -485,13 +524,25 @@ def headline(ctx: Ctx, L, args, out_line: dict):
         if sharded and timing:
             _pre_time(L, every=4, reset=True)
 
+    def reset_seeded():
+        # --dump-outputs: the shard refilled and the bucket sets from the first, so the
+        # state after the timed steps does not depend on how many steps warmed up
+        reset()
+        if args.dump_outputs:
+            timed_store.synth_fill(7)
+            k_step[0] = 0
+
     el = timed_steps(ctx, step, finish, args.steps, 0, ramp_s=max(0.0, 0.3 - (time.perf_counter() - t0)),
-                     reset=reset)
+                     reset=reset_seeded)
     k_ms, k_n = timed_store.kernel_time(reset=True)
     pre_ms, pre_n = _pre_time(L, every=0, reset=True) if sharded else (0.0, 0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "shard" if world == 1 else f"shard_rank{rank}", timed_store.values(),
+                     DUMP_BYTES // world)
     shuffled = None
     if not sharded:
         counts = timed_store.stats(reset=True)
+    if not sharded and args.full:
         # the arrival-order case: every step's 32 pushes in a new order (SHUFFLE_ORDERS
         # seeded orders, cycled), same store, warm
         cur[0] = shuffled_batches
@@ -548,19 +599,21 @@ def headline(ctx: Ctx, L, args, out_line: dict):
     if not sharded and k_n > 0:
         avg_s = k_ms / k_n / 1e3
         achieved = algo_per_rank / avg_s / 1e9
-        pk = stream_peaks(L, torch)
         kn = timed_store.kernel_name()
         out_line["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                                 "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                                 **traffic_for("config2", kn), "kernel": kn,
-                                "avg_kernel_us": round(avg_s * 1e6, 2), "launches": k_n,
-                                "measured_read_peak": round(pk["read"], 1),
-                                "frac_of_measured_read": round(achieved / pk["read"], 4),
-                                "measured_copy_peak": round(pk["copy"], 1)}
+                                "avg_kernel_us": round(avg_s * 1e6, 2), "launches": k_n}
+        if args.full:  # the streaming ceilings take runs of their own
+            pk = stream_peaks(L, torch)
+            out_line["roofline"].update({"measured_read_peak": round(pk["read"], 1),
+                                         "frac_of_measured_read": round(achieved / pk["read"], 4),
+                                         "measured_copy_peak": round(pk["copy"], 1)})
         out_line["pushes_per_step"] = {k: round(counts[k] / max(counts["chunks"], 1), 2)
                                                  for k in ("identity_pushes", "reused_pushes", "indexed_pushes")}
         out_line["spec_reruns"] = counts["spec_reruns"]
-        out_line["shuffled"] = shuffled
+        if args.full:
+            out_line["shuffled"] = shuffled
     elif pre_n > 0:
         # the pre-reduce pieces (k_reduce_rows in pre-reduce mode) are the dominant
         # kernel; per call they read the W pushes and write the full-model partial
@@ -1365,9 +1418,15 @@ def main():
     # ~0.2 s of warmup and ~0.4 s timed at N=1 by default
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=500)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: its arrival-order variants and measured stream peaks, the "
+                         "--legs and --sparse-steps legs, the native group at N > 1, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the shard the timed steps left (a seeded row sample, float32) and its float64 "
+                         "row sums as DIR/*.npy; the shard is refilled right before the timed steps")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline legs")
     ap.add_argument("--no-timing", action="store_true", help="no kernel timing events in the timed region")
-    ap.add_argument("--sparse-steps", type=int, default=20, help="config-3 sparse leg steps (0 = skip; N=1 only)")
+    ap.add_argument("--sparse-steps", type=int, default=20, help="--full: config-3 sparse leg steps (0 = skip; N=1 only)")
     ap.add_argument("--pieces", type=int, default=1, help="pre-reduce row slices per call (sharded path)")
     ap.add_argument("--sparse-cu-split", type=int, default=0,
                     help="config 3: CUs of the partition's stream (| pattern << 16; 0 = every CU for both)")
@@ -1386,11 +1445,12 @@ def main():
                     help="--emulate-rs: blocks of the ring reduce-scatter footprint (RCCL: one per channel)")
     ap.add_argument("--index-normal-prio", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--native-group", action="store_true",
-                    help="also run the config-2 workload through dml_group at N = 1 (always at N > 1)")
+                    help="also run the config-2 workload through dml_group at N = 1 (--full: always at N > 1)")
     ap.add_argument("--group", action="store_true",
                     help="use the sharded pre-reduce/reduce-scatter path even at N=1 (path check)")
     ap.add_argument("--legs", default="4,4w,5,4a",
-                    help="model-level config legs in the line (4, 4w = config 4 at W 8 and 32, 5, 4a; '' = none)")
+                    help="--full: model-level config legs in the line (4, 4w = config 4 at W 8 and 32, 5, 4a; "
+                         "'' = none)")
     ap.add_argument("--c4-pushes", type=int, default=16, help="config-4 full-range pushes per GPU (8.04 GB each)")
     ap.add_argument("--c4-order", choices=["asc", "perm"], default="asc",
                     help="config-4 row order per push: ascending (SURVEY §8d, keys implicit = row) or permuted")
@@ -1465,7 +1525,7 @@ def main():
 
     line: dict = {}
     headline(ctx, L, args, line)
-    legs = [x for x in args.legs.split(",") if x]
+    legs = [x for x in args.legs.split(",") if x] if args.full else []
     if "4" in legs:
         line["config4"] = leg_config4(ctx, L, args)
     if "4w" in legs:
@@ -1478,12 +1538,12 @@ def main():
         line["config5"] = leg_config5(ctx, L, args)
     if "4a" in legs:
         line["config4_ada"] = leg_config4_ada(ctx, L, args)
-    if (world > 1 and not args.rehearse_gloo) or args.native_group:
+    if (args.full and world > 1 and not args.rehearse_gloo) or args.native_group:
         line["native_group"] = guarded_leg(ctx, line, out, "native_group", lambda: leg_native_group(ctx, L, args),
                                            seconds=180.0)
-    if world == 1 and not args.group and args.sparse_steps > 0:
+    if args.full and world == 1 and not args.group and args.sparse_steps > 0:
         line["sparse"] = sparse_leg(ctx, L, args.sparse_steps, cpu=not args.no_cpu, cu_split=args.sparse_cu_split)
-    if rank == 0 and world == 1 and not args.no_cpu and not args.group:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not args.group:
         line["cpu_baseline"] = cpu_baseline()
     if args.rehearse_gloo and world > 1:
         # diagnostic only: the collectives ran over gloo through host memory with every

@@ -1,5 +1,6 @@
 # A/B of bench arguments on one box: ROUNDS alternating runs of `python bench.py $ARGS $A`
 # and `... $B`; prints each leg in LEGS (frac, kernel µs, floor fraction where the leg has one).
+# (legs other than the headline need --full in ARGS)
 set -e
 export TMPDIR=/tmp; mkdir -p gpurun_out
 for r in $(seq 1 ${ROUNDS:-3}); do

@@ -2,6 +2,7 @@
 # pass, then separate FETCH_SIZE and WRITE_SIZE counter passes (never combined
 # with tracing; each pass its own time limit, MI355X_MICROARCH.md rocprofv3 PMC).
 #   TAG=cfg5 ARGS="--config 5 --no-cpu" bash scripts/gpu_prof.sh
+# (the default line's legs run only with --full in ARGS)
 # Outputs gpurun_out/prof_<TAG>_{stats,fetch,write}/ ; scripts/summarize_profiles.py
 # turns them into profiles/<round>_<TAG>_* and the pmc_traffic.json entry.
 set -e

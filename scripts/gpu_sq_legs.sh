@@ -4,7 +4,7 @@
 set -e
 export TMPDIR=/tmp; mkdir -p gpurun_out
 O=$PWD/gpurun_out
-BA="--legs 4,4a,5 --sparse-steps 0 --no-cpu --steps 3 --warmup 1 --c4-steps 1 --c4-warmup 0 --c4a-steps 1 --c4a-warmup 1 --c5-steps 2 --c5-warmup 0"
+BA="--full --legs 4,4a,5 --sparse-steps 0 --no-cpu --steps 3 --warmup 1 --c4-steps 1 --c4-warmup 0 --c4a-steps 1 --c4a-warmup 1 --c5-steps 2 --c5-warmup 0"
 P1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU"
 P2="SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LEVEL_WAVES SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_INST_LEVEL_VMEM SQ_CYCLES"
 timeout -s KILL 240 rocprofv3 --pmc $P1 -d $O/sq1 -o run --output-format csv -- python3 bench.py $BA > $O/sq1.log 2>&1
