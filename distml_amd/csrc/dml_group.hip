@@ -310,6 +310,14 @@ int grow(void** p, int64_t* cap, int64_t need) {
 
 }  // namespace
 
+// Device push pointers are 4-byte aligned (include/distml_ps.h). An argument error like a
+// null pointer: refused before the group's state moves or the rank joins a collective.
+static bool push_ptrs_aligned(const void* const* bufs, int n) {
+    for (int i = 0; i < n; ++i)
+        if ((uintptr_t)bufs[i] & 3u) return false;
+    return true;
+}
+
 extern "C" {
 
 int dml_group_unique_id(uint8_t* out, int32_t cap) {
@@ -370,6 +378,7 @@ int dml_group_store(dml_group* g, dml_store** store) {
 int dml_group_push_full_range(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
     if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
         return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
     if (!g->plain)
         return set_error(DML_E_UNSUPPORTED, "the full-range pre-reduce path needs a plain-sum matrix (use dml_group_push_exchange)");
     GHIP(hipSetDevice(g->device));
@@ -410,6 +419,7 @@ int dml_group_push_full_range(dml_group* g, const void* const* dev_bufs, const i
 int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
     if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
         return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
     GHIP(hipSetDevice(g->device));
     // full-range calls still waiting for their reduce-scatter come first: the store
     // applies calls in order
@@ -519,6 +529,7 @@ int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int
 int dml_group_push_moments(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
     if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
         return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
     if (!g->desc.ada_grad || g->desc.value_type != DML_ELEMENT_TYPE_FLOAT)
         return set_error(DML_E_UNSUPPORTED, "the two-moment path is for AdaGrad (float) matrices");
     GHIP(hipSetDevice(g->device));
@@ -579,6 +590,7 @@ int dml_group_push_moments(dml_group* g, const void* const* dev_bufs, const int6
 int dml_group_push_local(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
     if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
         return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
     GHIP(hipSetDevice(g->device));
     if (g->xheld) {  // the last exchange call's slices
         GHIP(hipStreamSynchronize(g->rstream));

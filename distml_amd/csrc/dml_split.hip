@@ -156,6 +156,10 @@ extern "C" int dml_shard_split(const dml_desc* desc, int32_t cols, int64_t total
     if (!desc || total_rows <= 0 || world <= 0 || world > kMaxWorld || n < 0 || n > kMaxW ||
         (n > 0 && (!dev_bufs || !lens || !counts)))
         return set_error(DML_E_INVALID_ARG, "bad split arguments (world <= 64, n <= 64)");
+    // pushes and the output are 4-byte aligned (include/distml_ps.h): checked before any launch
+    bool aligned = ((uintptr_t)dev_out & 3u) == 0;
+    for (int b = 0; b < n; ++b) aligned = aligned && ((uintptr_t)dev_bufs[b] & 3u) == 0;
+    if (!aligned) return set_error(DML_E_INVALID_ARG, "device push or output pointer is not 4-byte aligned");
     if (desc->data_type == DML_DATA_TYPE_MATRIX && !desc->dense_column)
         return set_error(DML_E_UNSUPPORTED, "sparse-column matrix pushes are not supported");
     const int K = desc->key_type == 0 ? 4 : 8;

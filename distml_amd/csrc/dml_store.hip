@@ -43,6 +43,17 @@ static int set_err(int code, const std::string& msg) {
 }
 int dml::set_error(int code, const std::string& msg) { return set_err(code, msg); }
 
+// Device push pointers are 4-byte aligned (include/distml_ps.h): every kernel reads keys
+// as dwords and values with 4-byte-aligned 16-B loads. The entry points that take device
+// pushes refuse anything else before they launch or change state (dml_shard_split,
+// dml_split.hip, checks the same way).
+static const char* const kMisalignedPush = "device push pointer is not 4-byte aligned";
+static bool push_ptrs_aligned(const void* const* bufs, int n) {
+    for (int i = 0; i < n; ++i)
+        if ((uintptr_t)bufs[i] & 3u) return false;
+    return true;
+}
+
 #define HIPCHK(x)                                                                                  \
     do {                                                                                           \
         hipError_t e_ = (x);                                                                       \
@@ -1260,6 +1271,7 @@ int dml_store_push_batch_device(dml_store* s, const void* const* dev_bufs, const
     if (s->err) return set_err(s->err, "store is in a failed state (see dml_store_error_state)");
     for (int32_t i = 0; i < n; ++i)
         if (lens[i] < 0 || (lens[i] > 0 && !dev_bufs[i])) return set_err(DML_E_INVALID_ARG, "bad push buffer");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_err(DML_E_INVALID_ARG, kMisalignedPush);
     return run_batch(s, (const uint8_t* const*)dev_bufs, lens, n);
 }
 
@@ -1795,6 +1807,7 @@ int dml_reduce_buckets_dense(const dml_desc* desc, int64_t first_key, int64_t ro
                              const void* const* dev_bufs, const int64_t* lens, int32_t n, void* dev_out, void* stream) {
     if (!desc || !dev_out || rows <= 0 || cols <= 0 || n < 0 || (n > 0 && (!dev_bufs || !lens)))
         return set_err(DML_E_INVALID_ARG, "bad reduce arguments");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_err(DML_E_INVALID_ARG, kMisalignedPush);
     if (desc->data_type != 1 || !desc->dense_column || desc->ada_grad)
         return set_err(DML_E_UNSUPPORTED, "pre-reduce supports dense-column plain matrices");
     const int vt = desc->value_type;
@@ -2024,6 +2037,7 @@ int dml_prereduce_begin(const dml_desc* desc, int64_t first_key, int64_t rows, i
                         const int64_t* lens, int32_t n, void* stream, dml_prereduce** out) {
     if (!desc || !out || rows <= 0 || cols <= 0 || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
         return set_err(DML_E_INVALID_ARG, "bad pre-reduce arguments (n must be <= 64)");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_err(DML_E_INVALID_ARG, kMisalignedPush);
     // AdaGrad matrices: only the two-moment pieces (dml_prereduce_moments_piece)
     if (desc->data_type != 1 || !desc->dense_column || (desc->ada_grad && desc->value_type != DML_ELEMENT_TYPE_FLOAT))
         return set_err(DML_E_UNSUPPORTED, "pre-reduce supports dense-column matrices");
@@ -2373,6 +2387,7 @@ int dml_prereduce_begin_ctx(dml_prectx* x, const void* const* dev_bufs, const in
                             dml_prereduce** out) {
     if (!x || !out || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
         return set_err(DML_E_INVALID_ARG, "bad pre-reduce arguments (n must be <= 64)");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_err(DML_E_INVALID_ARG, kMisalignedPush);
     std::lock_guard<std::mutex> lk(x->mu);
     DeviceGuard g(x->device);
     // the ring's next workspace must have been ended: a call still holding it would

@@ -116,7 +116,19 @@ int dml_store_push_batch(dml_store* s, const uint8_t* const* bufs, const int64_t
 
 /* Same, for buckets already resident in device memory on the store's device
  * (the device-resident north-star path). Buffers must stay valid until the
- * next dml_store_flush (or any read call). */
+ * next dml_store_flush (or any read call).
+ *
+ * Device push placement (this call, dml_reduce_buckets_dense, dml_prereduce_begin,
+ * dml_prereduce_begin_ctx, dml_shard_split and the dml_group_push_* calls):
+ * every dev_bufs[i] is 4-byte aligned, nothing more; a pointer that is not gets
+ * DML_E_INVALID_ARG before anything is launched or any state changes. The group
+ * calls check it with their other arguments, before the group's state moves and
+ * before the rank joins the call's collective: like a null pointer it is a
+ * caller's error that every rank must avoid, not a failure the collective
+ * absorbs with zeros. A push is
+ * read only inside [dev_bufs[i], dev_bufs[i] + lens[i]), and never written, so
+ * pushes may lie back to back in one buffer (as the exchange path's receive
+ * buffer holds them) or against other live data. */
 int dml_store_push_batch_device(dml_store* s, const void* const* dev_bufs, const int64_t* lens, int32_t n);
 
 /* Read barrier: every accepted push is applied; returns any deferred error. */
@@ -274,7 +286,9 @@ int dml_store_apply_adagrad_moments_device(dml_store* s, const void* dev_src, in
 /* Ordered reduce of n device-resident full-range buckets into a dense device
  * buffer `dev_out` (rows*cols values of `value_type`, row = key - first_key):
  * out = b0 + b1 + ... in push order (rows no bucket touches are zero).
- * The multi-GPU pre-reduce before the reduce-scatter. Runs on `stream`. */
+ * The multi-GPU pre-reduce before the reduce-scatter. Runs on `stream`.
+ * Pushes: 4-byte aligned, read inside [ptr, ptr + len) only, may be adjacent
+ * (see dml_store_push_batch_device). */
 int dml_reduce_buckets_dense(const dml_desc* desc, int64_t first_key, int64_t rows, int32_t cols,
                              const void* const* dev_bufs, const int64_t* lens, int32_t n,
                              void* dev_out, void* stream);
@@ -287,7 +301,10 @@ int dml_reduce_buckets_dense(const dml_desc* desc, int64_t first_key, int64_t ro
  * index and every piece and reports key-out-of-matrix / repeated-row errors.
  * Each piece runs on its own `stream` argument (0 = the null stream), which may
  * differ from _begin's (the first such piece waits for the index on the host),
- * so the next call's index can overlap the current call's pieces. Opaque handle. */
+ * so the next call's index can overlap the current call's pieces. Opaque handle.
+ * Pushes: 4-byte aligned, read inside [ptr, ptr + len) only, may be adjacent
+ * (see dml_store_push_batch_device); a piece writes only its ntask_rows x cols
+ * values at dev_out. */
 typedef struct dml_prereduce dml_prereduce;
 int dml_prereduce_begin(const dml_desc* desc, int64_t first_key, int64_t rows, int32_t cols,
                         const void* const* dev_bufs, const int64_t* lens, int32_t n, void* stream,
@@ -325,7 +342,9 @@ int dml_prereduce_kernel_time(double* ms, int64_t* launches, int32_t reset);
  * dml_prereduce_stream_wait; _end then reports the call's errors as before.
  * dml_prectx_stats counts calls as dml_store_stats counts chunks. At most three
  * calls of one context may be outstanding (begun and not yet ended): a fourth
- * _begin_ctx returns DML_E_INVALID_ARG instead of reusing a busy workspace. */
+ * _begin_ctx returns DML_E_INVALID_ARG instead of reusing a busy workspace.
+ * Pushes: 4-byte aligned (DML_E_INVALID_ARG otherwise, before the context's
+ * ring moves), read inside [ptr, ptr + len) only, may be adjacent. */
 typedef struct dml_prectx dml_prectx;
 int dml_prectx_create(const dml_desc* desc, int64_t first_key, int64_t rows, int32_t cols, int32_t device,
                       dml_prectx** out);
@@ -347,7 +366,10 @@ int dml_prereduce_verify(dml_prereduce* p, int32_t* rerun);
  * dest d. Keys outside [0, total_rows) are dropped (the client's p.contains(k)).
  * Kernels run on `stream`; the call returns when dev_out is written.
  * DML_E_CAPACITY when out_cap is smaller than the kept bytes; world <= 64, n <= 64.
- * dev_out == NULL: counts only (nothing is copied). */
+ * dev_out == NULL: counts only (nothing is copied).
+ * Pushes and dev_out are 4-byte aligned (DML_E_INVALID_ARG otherwise, before any
+ * launch); pushes are read inside [ptr, ptr + len) only and may be adjacent; only
+ * the kept bytes at the head of dev_out are written, never a byte past out_cap. */
 int dml_shard_split(const dml_desc* desc, int32_t cols, int64_t total_rows, int32_t world,
                     const void* const* dev_bufs, const int64_t* lens, int32_t n, void* dev_out,
                     int64_t out_cap, int64_t* counts, void* stream);

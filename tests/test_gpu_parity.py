@@ -1133,18 +1133,9 @@ def test_shard_group_orders_after_producer_stream(oracle):
 
 
 def _np_split(recs_list, K, total_rows, world):
-    """Reference split for dml_shard_split: stable per-owner partition, dest-major."""
-    from distml_amd.datadesc import KeyRange
-    step = KeyRange(0, total_rows - 1).linearSplit(world)[0].size()
-    kdt = "<i4" if K == 4 else "<i8"
-    owners = []
-    for r in recs_list:
-        k = r[:, :K].copy().view(kdt).ravel().astype(np.int64)
-        o = np.where((k >= 0) & (k < total_rows), k // max(step, 1), world)
-        owners.append(np.minimum(o, world))
-    out = b"".join(r[o == d].tobytes() for d in range(world) for r, o in zip(recs_list, owners))
-    counts = [[int((o == d).sum()) for d in range(world)] for o in owners]
-    return out, counts
+    """Reference split for dml_shard_split (tests/geom.py: shared with test_gpu_geometry)."""
+    import geom
+    return geom.np_split(recs_list, K, total_rows, world)
 
 
 @pytest.mark.parametrize("case", [
@@ -1180,7 +1171,7 @@ def test_shard_split_kernel(case):
         recs.append(r)
     dev = [torch.from_numpy(r.reshape(-1)).cuda() for r in recs]
     cap = sum(d.numel() for d in dev)
-    out = torch.zeros(cap + 16, dtype=torch.uint8, device="cuda")
+    out = torch.zeros(cap, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     counts = HipOps().split(fmt, cols, total, world, [d.data_ptr() for d in dev], [d.numel() for d in dev],
                             out.data_ptr(), cap, torch.cuda.current_stream().cuda_stream)
