@@ -20,6 +20,9 @@
 // at dml_group_flush. The communicator comes from ncclCommInitRankConfig (the
 // channel count pinned, kRsChannels) with a unique id the caller distributes (the
 // JVM's control plane).
+// dml_group_push_chained is the order-exact alternative for plain fp32 / fp64
+// matrices: each shard's slice walks the ring of ranks over ncclSend / ncclRecv and
+// every rank adds its own pushes' rows to it in push order.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -106,6 +109,14 @@ struct dml_group {
     hipEvent_t mapplied[2] = {nullptr, nullptr};
     std::deque<dml_prereduce*> mpending;  // calls whose index errors are not yet collected
     int mk = 0;
+    // chained path (dml_group_push_chained), allocated on its first call: two buffer
+    // sets by call, each two slice buffers the ring steps alternate between (step t
+    // sums in place in the one that step t-1 received into, while the other receives)
+    void* cbuf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    std::vector<hipEvent_t> cev[2];  // per set: [step][sub-chunk] piece done, then [step][sub-chunk] received
+    hipEvent_t cready = nullptr;     // store stream: every earlier call's apply is enqueued before it
+    std::deque<dml_prereduce*> cpending;  // calls whose index errors are not yet collected
+    int ck = 0;
 };
 
 namespace {
@@ -189,24 +200,33 @@ int end_pending(dml_group* g, size_t keep) {
     return rc;
 }
 
-int end_moments(dml_group* g, size_t keep) {
+// The index errors (key outside the matrix, repeated row) of the moments / chained
+// calls still held, oldest first, down to `keep` of them.
+int end_handles(std::deque<dml_prereduce*>& q, size_t keep) {
     int rc = DML_OK;
-    while (g->mpending.size() > keep) {
-        dml_prereduce* p = g->mpending.front();
-        g->mpending.pop_front();
+    while (q.size() > keep) {
+        dml_prereduce* p = q.front();
+        q.pop_front();
         const int r = dml_prereduce_end(p);
         if (rc == DML_OK) rc = r;
     }
     return rc;
 }
+int end_moments(dml_group* g, size_t keep) { return end_handles(g->mpending, keep); }
+int end_chained(dml_group* g, size_t keep) { return end_handles(g->cpending, keep); }
 
 void group_free(dml_group* g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
     (void)end_pending(g, 0);
     (void)end_moments(g, 0);
+    (void)end_chained(g, 0);
     if (g->pctx) dml_prectx_destroy(g->pctx);
+    if (g->cready) (void)hipEventDestroy(g->cready);
     for (int i = 0; i < 2; ++i) {
+        for (void* b : g->cbuf[i])
+            if (b) (void)hipFree(b);
+        for (hipEvent_t e : g->cev[i]) (void)hipEventDestroy(e);
         if (g->mpart[i]) (void)hipFree(g->mpart[i]);
         if (g->mrecv[i]) (void)hipFree(g->mrecv[i]);
         if (g->mrs_done[i]) (void)hipEventDestroy(g->mrs_done[i]);
@@ -386,6 +406,7 @@ int dml_group_push_full_range(dml_group* g, const void* const* dev_bufs, const i
         GHIP(hipStreamSynchronize(g->rstream));
         GRC(hand_over(g));
     }
+    GRC(end_chained(g, 0));  // chained calls are committed on the store's stream already: their index errors
     GRC(ensure_partials(g));
     const int64_t S = g->step_rows, P = g->pieces;
     if (S % P) return set_error(DML_E_INVALID_ARG, "pieces must divide the linearSplit step");
@@ -424,6 +445,7 @@ int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int
     // full-range calls still waiting for their reduce-scatter come first: the store
     // applies calls in order
     GRC(end_pending(g, 0));
+    GRC(end_chained(g, 0));
     const int W = g->world;
     const int64_t K = g->desc.key_type == 0 ? 4 : 8;
     const int64_t stride = g->desc.data_type == DML_DATA_TYPE_MATRIX ? K + (int64_t)g->vbytes * g->cols
@@ -597,7 +619,127 @@ int dml_group_push_local(dml_group* g, const void* const* dev_bufs, const int64_
         GRC(hand_over(g));
     }
     GRC(end_pending(g, 0));  // full-range calls waiting for their reduce-scatter and apply
+    GRC(end_chained(g, 0));  // chained calls' commits are on the store's stream already: their index errors
     return dml_store_push_batch_device(g->store, dev_bufs, lens, n);
+}
+
+// Order-exact chained reduce-scatter (contract: include/distml_ps.h). At ring step t
+// rank r holds slice q = (r - t) mod N (the rows of shard q): it adds its pushes' rows
+// of q (a chain piece on cstream; step 0 starts from its own shard, later steps sum in
+// place in what arrived from r-1), then sends q to r+1 and receives slice q-1 from r-1
+// (one ncclSend + ncclRecv group on rstream). A slice goes in `pieces` sub-chunks:
+// sub-chunk k's transfer runs under sub-chunk k+1's piece. What step N-1 receives is
+// the rank's own slice after every rank's adds: the store commits it on its stream.
+// The whole call is enqueued with one host wait, the first piece's for the key index;
+// only then is the previous chained call's handle ended (its index errors; its pieces
+// have run by then, or are waited for), so the host runs one call ahead of the ring.
+// A local failure (first = a code) changes no send and no receive: the rank forwards
+// every slice as it holds it.
+int dml_group_push_chained(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
+    if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
+        return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
+    // the same answer on every rank, before any send: nobody waits for a peer
+    if (!g->plain || g->desc.value_type == DML_ELEMENT_TYPE_INT)
+        return set_error(DML_E_UNSUPPORTED,
+                         "the chained path sums plain fp32 / fp64 matrices (int32 and AdaGrad: use dml_group_push_exchange)");
+    GHIP(hipSetDevice(g->device));
+    if (g->xheld) {  // an exchange call's slices come first: the store applies calls in order
+        GHIP(hipStreamSynchronize(g->rstream));
+        GRC(hand_over(g));
+    }
+    const int W = g->world, P = g->pieces;
+    if (W == 1) {  // one owner: the store's own ordered push is the chain
+        GRC(end_pending(g, 0));
+        return dml_store_push_batch_device(g->store, dev_bufs, lens, n);
+    }
+    // earlier full-range calls: their applies go onto the store's stream now; what they
+    // report is returned after this call's ring (the rank never leaves the ring)
+    const int prior = end_pending(g, 0);
+    const int64_t C = g->cols;
+    const size_t rowb = (size_t)C * g->vbytes;
+    std::vector<int64_t> f((size_t)W), l((size_t)W);
+    GRC(dml_linear_split(0, g->total_rows - 1, W, f.data(), l.data()));
+    if (!g->cbuf[0][0]) {  // first chained call: a group that never makes one pays nothing
+        for (int i = 0; i < 2; ++i) {
+            for (int j = 0; j < 2; ++j) GHIP(hipMalloc(&g->cbuf[i][j], (size_t)g->step_rows * rowb));
+            g->cev[i].resize((size_t)2 * W * P, nullptr);
+            for (hipEvent_t& e : g->cev[i]) GHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        GHIP(hipEventCreateWithFlags(&g->cready, hipEventDisableTiming));
+    }
+    const int set = g->ck;
+    g->ck ^= 1;
+    int first = DML_OK;  // the rank's first local failure of this call
+    auto note = [&](int rc) {
+        if (rc != DML_OK && first == DML_OK) first = rc;
+    };
+    auto hip = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess) note(set_error(DML_E_HIP, std::string(what) + ": " + hipGetErrorString(e)));
+    };
+    // the key index of the rank's pushes over the whole model, on the side stream (it
+    // overlaps the previous call's tail); a push that is not whole records fails here
+    dml_prereduce* h = nullptr;
+    note(dml_prereduce_begin(&g->desc, 0, g->total_rows, g->cols, dev_bufs, lens, n, g->istream, &h));
+    // the shard as every earlier call leaves it: earlier pushes are retired (the store's
+    // value pointer is then current) and cstream waits for what the store's stream holds
+    uint64_t seq = 0;
+    void* shard = nullptr;
+    int rs = dml_store_push_seq(g->store, &seq);
+    if (rs == DML_OK) rs = dml_store_retire(g->store, seq);
+    note(rs);
+    GRC(dml_store_device_ptr(g->store, &shard));
+    hip(hipEventRecord(g->cready, g->sstream), "hipEventRecord");
+    hip(hipStreamWaitEvent(g->cstream, g->cready, 0), "hipStreamWaitEvent");
+    uint8_t* const B[2] = {(uint8_t*)g->cbuf[set][0], (uint8_t*)g->cbuf[set][1]};
+    hipEvent_t* const pdone = g->cev[set].data();
+    hipEvent_t* const rdone = pdone + (size_t)W * P;
+    const int nxt = (g->rank + 1) % W, prv = (g->rank + W - 1) % W;
+    int crc = DML_OK;  // the transfers' own status
+    // sub-chunk k of slice q: rows [r0, r0 + nr) of the slice (the last may be shorter, or empty)
+    auto sub = [&](int q, int k, int64_t* r0, int64_t* nr) {
+        const int64_t rows = l[(size_t)q] - f[(size_t)q] + 1, per = (rows + P - 1) / P;
+        *r0 = std::min<int64_t>((int64_t)k * per, rows);
+        *nr = std::min<int64_t>(per, rows - *r0);
+    };
+    for (int t = 0; t < W; ++t) {
+        const int q = (g->rank - t + W) % W, qin = (q + W - 1) % W;
+        uint8_t* const cur = B[t & 1];        // step t's slice (t > 0: arrived here in step t - 1)
+        uint8_t* const in = B[(t + 1) & 1];   // slice qin lands here
+        for (int k = 0; k < P; ++k) {
+            int64_t r0, nr, i0, ni;
+            sub(q, k, &r0, &nr);
+            sub(qin, k, &i0, &ni);
+            uint8_t* const out = cur + (size_t)r0 * rowb;
+            if (nr > 0) {
+                const uint8_t* const base = t == 0 ? (const uint8_t*)shard + (size_t)r0 * rowb : out;
+                if (t > 0) hip(hipStreamWaitEvent(g->cstream, rdone[(t - 1) * P + k], 0), "hipStreamWaitEvent");
+                if (first == DML_OK)
+                    note(dml_prereduce_chain_piece(h, nr, nr, f[(size_t)q] + r0, nr, base, out, g->cstream));
+                // a failed rank forwards the slice as it holds it (step 0: its own shard's rows)
+                if (first != DML_OK && t == 0)
+                    hip(hipMemcpyAsync(out, base, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+                hip(hipEventRecord(pdone[t * P + k], g->cstream), "hipEventRecord");
+                hip(hipStreamWaitEvent(g->rstream, pdone[t * P + k], 0), "hipStreamWaitEvent");
+            }
+            // every rank issues this group, empty sub-chunks included (zero bytes)
+            ncclResult_t r = ncclGroupStart();
+            if (r == ncclSuccess) r = ncclSend(out, (size_t)nr * rowb, ncclUint8, nxt, g->comm, g->rstream);
+            if (r == ncclSuccess) r = ncclRecv(in + (size_t)i0 * rowb, (size_t)ni * rowb, ncclUint8, prv, g->comm, g->rstream);
+            const ncclResult_t re = ncclGroupEnd();
+            if (r == ncclSuccess) r = re;
+            if (r != ncclSuccess && crc == DML_OK)
+                crc = set_error(DML_E_HIP, std::string("chained ncclSend/ncclRecv: ") + ncclGetErrorString(r));
+            hip(hipEventRecord(rdone[t * P + k], g->rstream), "hipEventRecord");
+        }
+    }
+    // home: step N-1 received the rank's own slice, every rank's adds in it
+    hip(hipStreamWaitEvent(g->sstream, rdone[(W - 1) * P + P - 1], 0), "hipStreamWaitEvent");
+    int commit = crc;
+    if (commit == DML_OK) commit = dml_store_assign_dense_device(g->store, B[W & 1], g->shard_rows * C);
+    if (h) g->cpending.push_back(h);
+    const int older = end_chained(g, 1);  // the previous chained call's key / repeated-row errors
+    return prior != DML_OK ? prior : first != DML_OK ? first : commit != DML_OK ? commit : older;
 }
 
 int dml_group_debug_fail_verify(dml_group* g, int32_t nth) {
@@ -618,6 +760,8 @@ int dml_group_flush(dml_group* g) {
     if (rc == DML_OK) rc = r1;
     const int rm = end_moments(g, 0);
     if (rc == DML_OK) rc = rm;
+    const int rch = end_chained(g, 0);
+    if (rc == DML_OK) rc = rch;
     for (hipStream_t s : {g->cstream, g->rstream})
         if (hipStreamSynchronize(s) != hipSuccess && rc == DML_OK) rc = set_error(DML_E_HIP, "group stream sync");
     for (hipEvent_t e : g->applied)

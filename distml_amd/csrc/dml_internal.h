@@ -129,10 +129,14 @@ enum MdMode : int {
 // reduces shard row  (t / block) * stride + off + t % block  (block == 0: row = t)
 // and writes it to out + t*cols (out == null: in place). Rows >= rows_total are
 // padding of linearSplit's short last shard: written as zeros.
+// kChain launches: the accumulator of task row t starts from base + t*cols (the
+// slice as it arrived; out == base works, every element is read and written by one
+// lane), and padding rows are copied from base.
 struct RowMap {
     int64_t block = 0, stride = 0, off = 0;
     int64_t rows_total = 0;
     void* out = nullptr;
+    const void* base = nullptr;
     // model row of task row t (rows <= INT32_MAX, a Java array: 32-bit division)
     __host__ __device__ inline int64_t row(int64_t t) const {
         if (!block) return t;
@@ -154,7 +158,19 @@ enum ReduceMode : int {
     kAdaGrad = 2,      // FloatMatrixStoreAdaGrad dense
     kRollbackI32 = 3,  // undo adds after the first negative (exact mod 2^32)
     kPreReduce = 4,    // multi-GPU pre-reduce: acc starts at 0, every row written
+    // Chained reduce-scatter step (f32 / f64): acc starts at RowMap::base, the pushes'
+    // records are added in push order as kAdd adds them, every row is written to
+    // RowMap::out; a row no push lists is copied bit for bit (no add of +0.0, which
+    // would turn -0.0 into +0.0). A handle whose index met a key outside the matrix
+    // or a repeated row adds nothing: every row is copied.
+    kChain = 5,
 };
+// kChain: the index's verdict, read by every wave (nothing of a failed call is added)
+__host__ __device__ inline bool ctrl_index_failed(const Ctrl* c) {
+    const unsigned long long cut = c->cutoff;
+    const unsigned int nd = c->no_dup;
+    return (cut != kNoPos) | (nd == 0u);
+}
 
 enum VType : int { kI32 = 0, kF32 = 1, kF64 = 3 };
 

@@ -292,15 +292,19 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
         const int cg = (int)(task - trow * ngroups);
         const int64_t row = rm.row(trow);
         T* const rowp = rm.out ? (T*)rm.out + trow * (int64_t)cols : shard + row * (int64_t)cols;
+        // kChain: the row as it arrived (may be rowp itself: this lane alone touches its elements)
+        const T* const basep = MODE == kChain ? (const T*)rm.base + trow * (int64_t)cols : nullptr;
         if (rm.block && row >= rm.rows_total) {  // padding row of a short last shard
 #pragma unroll
             for (int c = 0; c < CPW; ++c) {
                 const int32_t cc = ((cg * CPW + c) * 64 + lane) * VEC;
                 for (int e = 0; e < VEC; ++e)
-                    if (cc + e < cols) rowp[cc + e] = T(0);
+                    if (cc + e < cols) rowp[cc + e] = MODE == kChain ? basep[cc + e] : T(0);
             }
             break;
         }
+        // kChain: a call whose index failed adds nothing (every row is copied)
+        const int nbe = (MODE == kChain && ctrl_index_failed(ctrl)) ? 0 : nb;
         if (rowflag && rowflag[row]) break;  // a push repeats this row: the host replays it exactly
 
         int32_t c0[CPW];
@@ -345,6 +349,9 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
                 if (MODE == kPreReduce) {
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) acc[c][e] = T(0);
+                } else if (MODE == kChain) {
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) acc[c][e] = e < nv[c] ? basep[c0[c] + e] : T(0);
                 } else if (nv[c] == VEC) {
                     const u32x4 t = SNT ? ldg16_nt((const uint8_t*)prow) : ldg16((const uint8_t*)prow);
                     unpack<T>(t, acc[c]);
@@ -396,7 +403,7 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
         };
 
         const bool vec_ok = cols >= VEC;  // wave-uniform: vector loads for every active lane
-        for (int b0 = 0; b0 < nb; b0 += SG) {
+        for (int b0 = 0; b0 < nbe; b0 += SG) {
             // Wave-uniform scalar loads of 8 slots / push indices / bases at once;
             // every index < kMaxW is in bounds of the slot row and the kernarg table.
             int32_t rr[SG];
@@ -409,7 +416,7 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
                 const u64x8 pv = *(const u64x8*)(&bt.base[b0 + h]);
 #pragma unroll
                 for (int g = 0; g < 8; ++g) {
-                    const bool in = b0 + h + g < nb;
+                    const bool in = b0 + h + g < nbe;
                     gbv[h + g] = in ? gv[g] : INT_MAX;
                     bp[h + g] = (const uint8_t*)pv[g];
                     rr[h + g] = (in && gbv[h + g] <= cut_b) ? sv[g] : -1;
@@ -429,7 +436,7 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
                 if (!sub) continue;
                 int glast = s0;  // last live push of this sub-group (absent ones carry INT_MAX)
 #pragma unroll
-                for (int g = 0; g < G; ++g) glast = b0 + s0 + g < nb ? s0 + g : glast;
+                for (int g = 0; g < G; ++g) glast = b0 + s0 + g < nbe ? s0 + g : glast;
                 if (vec_ok && gbv[glast] < cut_b) {
                     // Fast path: G x CPW independent 16-B loads in flight, no branches
                     // between them; an absent slot / empty chunk re-reads the row start.
@@ -496,6 +503,10 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
             for (int c = 0; c < CPW; ++c)
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) acc[c][e] = T(0);
+            touched = true;
+        }
+        if (MODE == kChain && !touched) {  // no push lists the row: copied as it arrived
+            load_row();
             touched = true;
         }
         if (touched) {
@@ -585,7 +596,7 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
                                                      const uint32_t* __restrict__ rowflag, Ctrl* __restrict__ ctrl,
                                                      uint64_t tail_cut, RowMap rm) {
     constexpr int VEC = Elem<T>::VEC;
-    static_assert(MODE == kAdd || MODE == kAddCheckI32 || MODE == kPreReduce, "plain-sum modes only");
+    static_assert(MODE == kAdd || MODE == kAddCheckI32 || MODE == kPreReduce || MODE == kChain, "plain-sum modes only");
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // DEPTH 3 (rows that are not whole lines, e.g. config 5's 4000-B rows): XCD-
@@ -617,6 +628,7 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
 
     int64_t row[RPW];
     T* rowp[RPW];
+    const T* basep[RPW];  // kChain: the rows as they arrived (may be rowp: a lane alone touches its elements)
     unsigned live = 0;
     const uint8_t* fb = nullptr;  // a readable address inside a live row (target of absent loads)
 #pragma unroll
@@ -625,13 +637,14 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
         const int64_t tr = trow < rows ? trow : tb * RPW;
         row[r] = rm.row(tr);
         rowp[r] = rm.out ? (T*)rm.out + tr * (int64_t)cols : shard + row[r] * (int64_t)cols;
+        basep[r] = MODE == kChain ? (const T*)rm.base + tr * (int64_t)cols : nullptr;
         if (trow >= rows) continue;
-        if (rm.block && row[r] >= rm.rows_total) {  // padding row of a short last shard: zeros
+        if (rm.block && row[r] >= rm.rows_total) {  // padding row of a short last shard: zeros (kChain: copied)
 #pragma unroll
             for (int c = 0; c < CPW; ++c)
 #pragma unroll
                 for (int e = 0; e < VEC; ++e)
-                    if (e < nv[c]) rowp[r][c0[c] + e] = T(0);
+                    if (e < nv[c]) rowp[r][c0[c] + e] = MODE == kChain ? basep[r][c0[c] + e] : T(0);
             continue;
         }
         // a push repeats this row: the host replays it exactly (a keeping chunk's index
@@ -639,7 +652,7 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
         if (rowflag && !bt.keeps && rowflag[row[r]]) continue;
         // a row no push of the chunk lists: its shard row is neither read nor written
         // (the index marked the listed ones; the load runs beside the flag load above)
-        if (MODE != kPreReduce && bt.listed && !bt.listed[row[r]]) continue;
+        if (MODE != kPreReduce && MODE != kChain && bt.listed && !bt.listed[row[r]]) continue;
         live |= 1u << r;
         if (!fb) fb = (const uint8_t*)rowp[r];
     }
@@ -665,9 +678,21 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
             ident = ctrl->ident;
         }
     }
-    if constexpr (MODE == kPreReduce)
+    if constexpr (MODE == kPreReduce || MODE == kChain)
         if (bt.ident_ok) ident = ctrl->ident;  // verified before the launch: slot = row, no key checks
 
+    if constexpr (MODE == kChain) {
+        // a call whose index failed (key outside the matrix, repeated row) adds nothing:
+        // the wave's rows are copied as they arrived
+        if (cut != kNoPos || ctrl->no_dup == 0u) {
+            for (int r = 0; r < RPW; ++r) {
+                if (!(live >> r & 1u)) continue;
+                for (int c = 0; c < CPW; ++c)
+                    for (int e = 0; e < nv[c]; ++e) rowp[r][c0[c] + e] = basep[r][c0[c] + e];
+            }
+            return;
+        }
+    }
     if (cut != kNoPos) {
         // Error batch: element-wise RMW of the wave's rows in place, pushes in order,
         // stopping at the cutoff byte (the state the reference leaves when it throws).
@@ -710,7 +735,9 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
         for (int c = 0; c < CPW; ++c) {
             const bool ld = MODE != kPreReduce && (live >> r & 1u);
             // the input row: in place, or the speculative chunk's input buffer
-            const T* const lrow = (MODE == kAdd && bt.src) ? (const T*)bt.src + row[r] * (int64_t)cols : rowp[r];
+            const T* const lrow = MODE == kChain                 ? basep[r]
+                                  : (MODE == kAdd && bt.src) ? (const T*)bt.src + row[r] * (int64_t)cols
+                                                             : rowp[r];
             if (ld && nv[c] == VEC) {
                 unpack<T>(ldg16((const uint8_t*)(lrow + c0[c])), acc[r][c]);
             } else {
@@ -979,7 +1006,8 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
             }
         }
     }
-    if (MODE == kPreReduce) touched = live;  // every pre-reduce row is written (zeros if no push has it)
+    // every pre-reduce row is written (zeros if no push has it); every chain row (as it arrived)
+    if (MODE == kPreReduce || MODE == kChain) touched = live;
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
         if (!(touched >> r & 1u)) continue;
@@ -1027,7 +1055,7 @@ __global__ __launch_bounds__(256) void k_reduce_flat(T* __restrict__ shard, int6
                                                      Ctrl* __restrict__ ctrl, uint64_t tail_cut, RowMap rm) {
     constexpr int VEC = Elem<T>::VEC;
     constexpr int RMAX = 16;
-    static_assert(MODE == kAdd || MODE == kPreReduce, "plain sums only");
+    static_assert(MODE == kAdd || MODE == kPreReduce || MODE == kChain, "plain sums only");
     __shared__ int32_t s_slot[4][RMAX * kMaxW];  // per wave: [row][push], -1 = no record / skipped row
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1048,8 +1076,11 @@ __global__ __launch_bounds__(256) void k_reduce_flat(T* __restrict__ shard, int6
             ident = ctrl->ident;
         }
     }
-    if constexpr (MODE == kPreReduce)
+    if constexpr (MODE == kPreReduce || MODE == kChain)
         if (bt.ident_ok) ident = ctrl->ident;  // verified before the launch (k_ident_full)
+    // kChain: a call whose index failed (key outside the matrix, repeated row) adds
+    // nothing: no row has a record, every row is copied as it arrived
+    const bool dead = MODE == kChain && (cut != kNoPos || ctrl->no_dup == 0u);
     const int NV = cols / VEC;
     const int nrow = (int)(rows - t0 < (int64_t)R ? rows - t0 : (int64_t)R);
     const int ss = slot_stride(nb);
@@ -1075,7 +1106,7 @@ __global__ __launch_bounds__(256) void k_reduce_flat(T* __restrict__ shard, int6
         const int rl = e / nb, b = e - rl * nb;
         const int64_t mr = model_row(t0 + rl);
         int32_t v = -1;
-        if (!(((padm | flg) >> rl) & 1u)) {
+        if (!(((padm | flg) >> rl) & 1u) && !dead) {
             if (ctrl_identity(ctrl, ident, b)) {  // identity push: record = row
                 v = mr < bt.nrec[b] ? (int32_t)mr : -1;
             } else {
@@ -1108,11 +1139,14 @@ __global__ __launch_bounds__(256) void k_reduce_flat(T* __restrict__ shard, int6
         const bool flagged = (flg >> rlj) & 1u;
         const bool o = v < nvec && !pad && !flagged;
         on |= (o ? 1u : 0u) << j;
-        wr |= ((v < nvec && (MODE == kPreReduce ? !flagged : o)) ? 1u : 0u) << j;
-        if (MODE != kPreReduce && o) {
-            // the input row: in place, or the speculative chunk's input buffer
-            const T* const ip = (MODE == kAdd && bt.src) ? (const T*)bt.src + mr * (int64_t)cols + cvj * VEC
-                                                         : out_ptr(rlj, cvj);
+        wr |= ((v < nvec && ((MODE == kPreReduce || MODE == kChain) ? !flagged : o)) ? 1u : 0u) << j;
+        if (MODE == kChain ? v < nvec : (MODE != kPreReduce && o)) {
+            // the input row: in place, or the speculative chunk's input buffer; kChain:
+            // the slice as it arrived, padding rows included (may be the output itself:
+            // this lane alone reads and writes the vector)
+            const T* const ip = MODE == kChain ? (const T*)rm.base + ((t0 + rlj) * (int64_t)cols + cvj * VEC)
+                                : (MODE == kAdd && bt.src) ? (const T*)bt.src + mr * (int64_t)cols + cvj * VEC
+                                                           : out_ptr(rlj, cvj);
             unpack<T>(ldg16((const uint8_t*)ip), acc[j]);
         } else {
 #pragma unroll
@@ -1120,7 +1154,7 @@ __global__ __launch_bounds__(256) void k_reduce_flat(T* __restrict__ shard, int6
         }
     }
     bool bad = false;
-    if (cut != kNoPos) {
+    if (MODE != kChain && cut != kNoPos) {
         // error batch: element by element, pushes in order, up to the cutoff byte
         const int cut_b = (int)(cut >> 40);
         const uint64_t cut_off = cut & kOffMask;
@@ -1212,7 +1246,7 @@ __global__ __launch_bounds__(NW * 64) void k_flat_ident(T* __restrict__ shard, i
                                                         const Batch bt, int nb, int64_t stride, int K,
                                                         Ctrl* __restrict__ ctrl, RowMap rm) {
     constexpr int VEC = Elem<T>::VEC;
-    static_assert(MODE == kAdd || MODE == kPreReduce, "plain sums only");
+    static_assert(MODE == kAdd || MODE == kPreReduce || MODE == kChain, "plain sums only");
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t t0 = (xcd_block() * NW + wid) * R;
@@ -1250,6 +1284,14 @@ __global__ __launch_bounds__(NW * 64) void k_flat_ident(T* __restrict__ shard, i
             const __amdgpu_buffer_rsrc_t is = buf_rsrc(ib, sspan);
 #pragma unroll
             for (int j = 0; j < J; ++j) unpack<T>(ldb16_nt(is, soff[j]), acc[j]);
+        } else if constexpr (MODE == kChain) {
+            // the slice as it arrived, task-row order like the output (ooff; padding rows
+            // included: they pass through). May be the output itself: a lane reads its
+            // vectors here and writes the same ones after the block barrier.
+            const __amdgpu_buffer_rsrc_t is =
+                buf_rsrc((const T*)rm.base + t0 * (int64_t)cols, (uint32_t)(nrow * cols * (int64_t)sizeof(T)));
+#pragma unroll
+            for (int j = 0; j < J; ++j) unpack<T>(ldb16_nt(is, ooff[j]), acc[j]);
         } else {
 #pragma unroll
             for (int j = 0; j < J; ++j)
@@ -1274,6 +1316,9 @@ __global__ __launch_bounds__(NW * 64) void k_flat_ident(T* __restrict__ shard, i
             for (int j = 0; j < J; ++j) {
                 T u[VEC];
                 unpack<T>(raw[j], u);
+                // kChain: a padding row has no record and passes through bit for bit
+                // (an add of the range check's +0.0 would turn -0.0 into +0.0)
+                if (MODE == kChain && loff[j] == kBufOff) continue;
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) acc[j][e] = Elem<T>::add(acc[j][e], u[e]);
             }
@@ -1615,7 +1660,8 @@ static hipError_t launch_auto(void* shard, int64_t rows, int32_t cols, const Bat
                                                      slot, rowflag, ctrl, tail_cut, ada, st, nblocks_out, ev, rm)
 #define DML_LFN(G, CPW, RPW) launch_reduce_t<T, MODE, G, true, 4, 1, CPW, RPW, true>(shard, rows, cols, bt, nb, \
                                                      stride, K, slot, rowflag, ctrl, tail_cut, ada, st, nblocks_out, ev, rm, 0)
-        if (MODE != kPreReduce) {
+        // (kChain keeps the pre-reduce instantiation's loads and stores of each shape below)
+        if (MODE != kPreReduce && MODE != kChain) {
             // Rows of >= 4 chunks that do not fill them (config 5's 4000-B int32 rows in
             // 4004-B records): cached record loads (the line two neighbouring records
             // share is fetched once) and 2-wave blocks (a finished block frees its slot
@@ -1717,6 +1763,11 @@ hipError_t launch_flat_ident(int vtype, int mode, void* shard, int64_t rows, int
                              int64_t stride, int K, Ctrl* ctrl, hipStream_t st, int64_t* nblocks_out, LaunchEv ev,
                              RowMap rm) {
 #define DML_FI(T, M) launch_flat_ident_t<T, M>(shard, rows, cols, bt, nb, stride, K, ctrl, st, nblocks_out, ev, rm)
+    if (mode == kChain) {
+        if (vtype == kF32) return DML_FI(float, kChain);
+        if (vtype == kF64) return DML_FI(double, kChain);
+        return hipErrorInvalidValue;
+    }
     if (vtype == kF32) return mode == kAdd ? DML_FI(float, kAdd) : DML_FI(float, kPreReduce);
     if (vtype == kI32) return mode == kAdd ? DML_FI(int32_t, kAdd) : DML_FI(int32_t, kPreReduce);
     if (vtype == kF64) return mode == kAdd ? DML_FI(double, kAdd) : DML_FI(double, kPreReduce);
@@ -1729,7 +1780,8 @@ hipError_t launch_flat_ident(int vtype, int mode, void* shard, int64_t rows, int
 // lists at least half the rows (dense pushes; sparse ones keep the pair-packed
 // k_reduce_rows / k_reduce).
 bool use_flat(int vtype, int mode, int32_t cols, const Batch& bt, int nb, int64_t rows) {
-    if (mode != kAdd && mode != kPreReduce && !(mode == kAdaGrad && vtype == kF32 && nb <= 4)) return false;
+    if (mode != kAdd && mode != kPreReduce && mode != kChain && !(mode == kAdaGrad && vtype == kF32 && nb <= 4))
+        return false;
     const int VEC = vtype == kF64 ? 2 : 4;
     const int elem = vtype == kF64 ? 8 : 4;
     if (cols % VEC || (int64_t)cols * elem >= 4096 || nb <= 0) return false;
@@ -1991,6 +2043,11 @@ hipError_t launch_reduce(int vtype, int mode, void* shard, int64_t rows, int32_t
             return rm.block || rm.out ? hipErrorInvalidValue
                                       : launch_ada_flat(shard, rows, cols, bt, nb, stride, K, slot, rowflag, ctrl,
                                                         tail_cut, ada, st, nblocks_out, ev);
+        if (mode == kChain) {
+            if (vtype == kF32) return DML_F(float, kChain);
+            if (vtype == kF64) return DML_F(double, kChain);
+            return hipErrorInvalidValue;
+        }
         if (vtype == kF32) return mode == kAdd ? DML_F(float, kAdd) : DML_F(float, kPreReduce);
         if (vtype == kI32) return mode == kAdd ? DML_F(int32_t, kAdd) : DML_F(int32_t, kPreReduce);
         if (vtype == kF64) return mode == kAdd ? DML_F(double, kAdd) : DML_F(double, kPreReduce);
@@ -2000,6 +2057,7 @@ hipError_t launch_reduce(int vtype, int mode, void* shard, int64_t rows, int32_t
         if (mode == kAdd) return DML_A(float, kAdd);
         if (mode == kAdaGrad) return DML_A(float, kAdaGrad);
         if (mode == kPreReduce) return DML_A(float, kPreReduce);
+        if (mode == kChain) return DML_A(float, kChain);
     } else if (vtype == kI32) {
         if (mode == kAdd) return DML_A(int32_t, kAdd);
         if (mode == kAddCheckI32) return DML_A(int32_t, kAddCheckI32);
@@ -2007,6 +2065,7 @@ hipError_t launch_reduce(int vtype, int mode, void* shard, int64_t rows, int32_t
     } else if (vtype == kF64) {
         if (mode == kAdd) return DML_A(double, kAdd);
         if (mode == kPreReduce) return DML_A(double, kPreReduce);
+        if (mode == kChain) return DML_A(double, kChain);
     }
 #undef DML_A
     return hipErrorInvalidValue;

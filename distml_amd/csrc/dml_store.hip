@@ -1732,6 +1732,22 @@ int dml_store_apply_dense_device(dml_store* s, const void* dev_src, int64_t elem
     return DML_OK;
 }
 
+int dml_store_assign_dense_device(dml_store* s, const void* dev_src, int64_t elems) {
+    if (int rc = check_store(s)) return rc;
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceGuard g(s->device);
+    if (!s->is_matrix || s->adagrad || !s->desc.dense_column)
+        return set_err(DML_E_UNSUPPORTED, "assign: plain dense-column matrices (f32 / f64 / i32)");
+    // every accepted push is retired first: s->data is then the buffer the last of
+    // them wrote (a speculative chunk commits the store's second buffer at its retire)
+    if (int rc = retire_all(s)) return rc;
+    if (int rc = collect_apply_check(s, false)) return rc;
+    if (s->err) return set_err(s->err, "store is in a failed state (see dml_store_error_state)");
+    if (!dev_src || elems != s->rows * s->cols) return set_err(DML_E_INVALID_ARG, "assign size mismatch");
+    HIPCHK(hipMemcpyAsync(s->data, dev_src, (size_t)elems * (size_t)s->V, hipMemcpyDeviceToDevice, s->stream));
+    return DML_OK;
+}
+
 int dml_store_apply_adagrad_moments_device(dml_store* s, const void* dev_src, int64_t rows) {
     if (int rc = check_store(s)) return rc;
     std::lock_guard<std::mutex> lk(s->mu);
@@ -1767,6 +1783,10 @@ struct WsLease {
     size_t bytes = 0;
     bool clean = false;     // slot table all -1 and rowflags 0 (left so by a clearing pre-reduce)
     Ctrl* hctrl = nullptr;  // pinned host copy of the Ctrl (read without touching a stream)
+    // the model rows `clean` was established for: a lease serves any model that fits, and
+    // a call of another size lays the table and the rowflags out elsewhere (entries a
+    // larger, failed call left beyond a smaller call's table are still there)
+    int64_t clean_rows = 0;
 };
 static std::mutex g_ws_mu;
 static std::unordered_map<int, std::vector<WsLease>> g_ws_free;
@@ -1899,6 +1919,8 @@ struct dml_prereduce {
     std::vector<PieceRec> prec;  // the pieces as launched (a failed verification re-runs them)
     hipEvent_t rerun_ev = nullptr;
     const Ctrl* hidx = nullptr;  // the workspace's Ctrl as the index left it (speculative calls of the flat shape)
+    bool chain_checked = false;  // the first chain piece decided about the up-front identity check
+    bool slots_unread = false;   // that check ran after the index: the pieces leave the filled slot table as it is
 };
 
 // Pre-reduce context (dml_prectx_*): the sharded path's pre-reduce with the
@@ -2076,7 +2098,7 @@ int dml_prereduce_begin(const dml_desc* desc, int64_t first_key, int64_t rows, i
     p->ws = lease.ptr;
     p->ws_bytes = lease.bytes;
     p->hctrl = lease.hctrl;
-    const bool clean = lease.clean;
+    const bool clean = lease.clean && lease.clean_rows == rows;
     p->ctrl = (Ctrl*)p->ws;
     p->slot = (int32_t*)(p->ws + sizeof(Ctrl));
     p->rowflag = (uint32_t*)(p->ws + sizeof(Ctrl) + sb);
@@ -2149,11 +2171,34 @@ int dml_prereduce_moments_piece(dml_prereduce* p, int64_t row_block, int64_t row
     return DML_OK;
 }
 
-int dml_prereduce_piece(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off, int64_t ntask_rows,
-                        void* dev_out, void* stream) {
-    if (!p || !dev_out || row_block <= 0 || ntask_rows < 0) return set_err(DML_E_INVALID_ARG, "bad piece arguments");
-    if (p->desc.ada_grad) return set_err(DML_E_UNSUPPORTED, "AdaGrad pre-reduce: dml_prereduce_moments_piece");
+}  // extern "C"
+
+// One piece of a pre-reduce handle: `mode` kPreReduce (dml_prereduce_piece: sums from
+// zero) or kChain (dml_prereduce_chain_piece: sums onto dev_base, a chained
+// reduce-scatter step). Row map, stream rule, completion event and timing are shared.
+static int prereduce_piece(dml_prereduce* p, int mode, int64_t row_block, int64_t row_stride, int64_t row_off,
+                           int64_t ntask_rows, const void* dev_base, void* dev_out, void* stream) {
     hipStream_t st = (hipStream_t)stream;  // as given: 0 is HIP's null stream
+    if (mode == kChain && !p->chain_checked) {
+        // Ascending full-range pushes of a flat shape (config 4's case): verify every
+        // key up front (k_ident_full), behind the index on its stream, so the pieces
+        // take slot = row and, once the host has seen the verdict, k_flat_ident.
+        // Complete, not speculative: a chained slice leaves the rank when its piece
+        // ends. (dml_prereduce_begin does this itself for slot tables beyond the
+        // caches; the table the index filled is then not read, so it is not clean.)
+        p->chain_checked = true;
+        bool full = p->nb > 0 && !p->bt.ident_ok && use_flat(p->desc.value_type, kChain, p->cols, p->bt, p->nb, p->rows);
+        for (int j = 0; j < p->nb && full; ++j) full = p->bt.nrec[j] == p->rows;
+        if (full) {
+            HIPCHK(launch_ident_full(p->bt, p->nb, p->rows, p->stride, p->K, p->first, p->rows, p->ctrl, p->stream));
+            p->bt.ident_ok = 1;
+            p->slots_unread = true;
+            HIPCHK(hipMemcpyAsync(p->hctrl, p->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, p->stream));
+            HIPCHK(hipEventRecord(p->idx_ev, p->stream));
+            p->idx_waited = false;
+        }
+        if (p->bt.ident_ok) p->hidx = p->hctrl;  // the verdict k_flat_ident is chosen from
+    }
     if (st != p->stream && !p->idx_waited) {
         // pieces on another stream (the index ran on a side stream, overlapping the
         // caller's previous work): wait for the index on the host, then enqueue the
@@ -2167,6 +2212,7 @@ int dml_prereduce_piece(dml_prereduce* p, int64_t row_block, int64_t row_stride,
     rm.off = row_off;
     rm.rows_total = p->rows;
     rm.out = dev_out;
+    rm.base = dev_base;
     AdaArgs none{};
     if (!p->last_ev) HIPCHK(hipEventCreateWithFlags(&p->last_ev, hipEventDisableTiming));
     // the piece's completion event rides in its dispatch packet (no marker packet between pieces)
@@ -2196,13 +2242,13 @@ int dml_prereduce_piece(dml_prereduce* p, int64_t row_block, int64_t row_stride,
             std::lock_guard<std::mutex> lk(p->ctx->mu);
             p->ctx->st.ident_launches += 1;
         }
-        HIPCHK(launch_flat_ident(p->desc.value_type, kPreReduce, dev_out, ntask_rows, p->cols, p->bt, p->nb, p->stride,
+        HIPCHK(launch_flat_ident(p->desc.value_type, mode, dev_out, ntask_rows, p->cols, p->bt, p->nb, p->stride,
                                  p->K, p->ctrl, st, nullptr, ev, rm));
     } else
-        HIPCHK(launch_reduce(p->desc.value_type, kPreReduce, dev_out, ntask_rows, p->cols, p->bt, p->nb, p->stride,
+        HIPCHK(launch_reduce(p->desc.value_type, mode, dev_out, ntask_rows, p->cols, p->bt, p->nb, p->stride,
                              p->K, p->slot, nullptr, p->ctrl, kNoPos, none, st, nullptr, ev, rm));
     p->done_ev = ev.stop;
-    p->prec.push_back({row_block, row_stride, row_off, ntask_rows, dev_out});
+    if (mode == kPreReduce) p->prec.push_back({row_block, row_stride, row_off, ntask_rows, dev_out});
     // model rows this piece covered: blocks of row_block task rows at row_off + q*row_stride
     for (int64_t t0 = 0; t0 < ntask_rows; t0 += row_block) {
         const int64_t lo = (t0 / row_block) * row_stride + row_off;
@@ -2211,6 +2257,28 @@ int dml_prereduce_piece(dml_prereduce* p, int64_t row_block, int64_t row_stride,
     }
     p->last_st = st;
     return DML_OK;
+}
+
+extern "C" {
+
+int dml_prereduce_piece(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off, int64_t ntask_rows,
+                        void* dev_out, void* stream) {
+    if (!p || !dev_out || row_block <= 0 || ntask_rows < 0) return set_err(DML_E_INVALID_ARG, "bad piece arguments");
+    if (p->desc.ada_grad) return set_err(DML_E_UNSUPPORTED, "AdaGrad pre-reduce: dml_prereduce_moments_piece");
+    return prereduce_piece(p, kPreReduce, row_block, row_stride, row_off, ntask_rows, nullptr, dev_out, stream);
+}
+
+int dml_prereduce_chain_piece(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
+                              int64_t ntask_rows, const void* dev_base, void* dev_out, void* stream) {
+    if (!p || !dev_base || !dev_out || row_block <= 0 || ntask_rows < 0)
+        return set_err(DML_E_INVALID_ARG, "bad chain piece arguments");
+    if (p->desc.ada_grad || (p->desc.value_type != DML_ELEMENT_TYPE_FLOAT && p->desc.value_type != DML_ELEMENT_TYPE_DOUBLE))
+        return set_err(DML_E_UNSUPPORTED,
+                       "chained pieces: plain fp32 / fp64 matrices (int32 and AdaGrad: dml_group_push_exchange)");
+    // what a chain piece writes is forwarded at once: a speculative handle's verdict
+    // (dml_prereduce_verify) would come after the slice has left the rank
+    if (p->ctx) return set_err(DML_E_UNSUPPORTED, "chained pieces need dml_prereduce_begin (no speculative context)");
+    return prereduce_piece(p, kChain, row_block, row_stride, row_off, ntask_rows, dev_base, dev_out, stream);
 }
 
 int dml_prereduce_timing(int32_t every) {
@@ -2307,9 +2375,13 @@ int dml_prereduce_end(dml_prereduce* p) {
     else if (h.no_dup == 0u) rc = set_err(DML_E_UNSUPPORTED, "pre-reduce: a push repeats a row");
     // after a failed sync the device state is unknown: drop the lease. A normal chunk
     // whose pieces reduced every row through the clearing kernel left the table clean.
-    const bool clean = rc == DML_OK && p->rows_done == p->rows &&
+    // (a chained call's late identity check: the pushes it confirmed left their indexed
+    // slots unread and uncleared; pushes it rejected were read and cleared like any other)
+    const uint64_t pushes = p->nb >= 64 ? ~0ull : (1ull << p->nb) - 1ull;
+    if (p->slots_unread && !(h.ident & pushes)) p->slots_unread = false;
+    const bool clean = rc == DML_OK && !p->slots_unread && p->rows_done == p->rows &&
                        reduce_clears_slots(p->desc.value_type, kPreReduce, p->cols);
-    if (e == hipSuccess) ws_release(p->device, WsLease{p->ws, p->ws_bytes, clean, p->hctrl});
+    if (e == hipSuccess) ws_release(p->device, WsLease{p->ws, p->ws_bytes, clean, p->hctrl, p->rows});
     prereduce_free(p);
     return rc;
 }

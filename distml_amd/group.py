@@ -25,6 +25,11 @@ of one pre-reduced sum is not seen (the reference would throw there) — the
 divergence SURVEY.md §8c names for batched reduces. push_exchange() applies
 int32 pushes exactly, intermediates included.
 
+The order-exact chained reduce-scatter (dml_group_push_chained) is
+bound by NativeShardGroup.push_chained only — the native group is the one the JNI
+deploys; this torch ShardGroup has no chained path. HipOps.chain_piece and
+HipOps.assign expose its two building blocks.
+
 Buffer contract of the asynchronous paths (push_full_range, push_exchange,
 push_local): the push buffers must stay allocated and unmodified until flush()
 — the same contract as dml_store_push_batch_device. The group orders its own
@@ -68,6 +73,17 @@ class HipOps:
     def piece(self, h, block: int, stride: int, off: int, ntask_rows: int, out_ptr: int, stream: int) -> None:
         check(_lib.load().dml_prereduce_piece(C.c_void_p(h), block, stride, off, ntask_rows, C.c_void_p(out_ptr),
                                               C.c_void_p(stream)))
+
+    def chain_piece(self, h, block: int, stride: int, off: int, ntask_rows: int, base_ptr: int, out_ptr: int,
+                    stream: int) -> None:
+        """One chained reduce-scatter step (dml_prereduce_chain_piece): out = base + the
+        handle's pushes' rows, in push order; out_ptr == base_ptr sums in place."""
+        check(_lib.load().dml_prereduce_chain_piece(C.c_void_p(h), block, stride, off, ntask_rows,
+                                                    C.c_void_p(base_ptr), C.c_void_p(out_ptr), C.c_void_p(stream)))
+
+    def assign(self, store: DataStore, src_ptr: int, elems: int) -> None:
+        """shard = src (dml_store_assign_dense_device): the owner's commit of a chained slice."""
+        check(_lib.load().dml_store_assign_dense_device(store._h, C.c_void_p(src_ptr), elems), store)
 
     def end(self, h) -> None:
         check(_lib.load().dml_prereduce_end(C.c_void_p(h)))
@@ -689,6 +705,15 @@ class NativeShardGroup:
         ptrs = (C.c_void_p * max(n, 1))(*dev_ptrs)
         ls = (C.c_int64 * max(n, 1))(*lens)
         check(self._L.dml_group_push_local(C.c_void_p(self._h), ptrs, ls, n), self.store)
+
+    def push_chained(self, dev_ptrs: Sequence[int], lens: Sequence[int]) -> None:
+        """The order-exact chained reduce-scatter (dml_group_push_chained), fp32 / fp64 plain
+        matrices: shard s ends byte-equal to a reference store fed rank s's pushes, then
+        rank s+1's, ..., rank s-1's. Ranks may pass different numbers of pushes."""
+        n = len(dev_ptrs)
+        ptrs = (C.c_void_p * max(n, 1))(*dev_ptrs)
+        ls = (C.c_int64 * max(n, 1))(*lens)
+        check(self._L.dml_group_push_chained(C.c_void_p(self._h), ptrs, ls, n), self.store)
 
     def debug_fail_verify(self, nth: int) -> None:
         """Fault injection (tests): the nth full-range call finished from now fails its verdict."""

@@ -274,6 +274,19 @@ int dml_store_kernel_name(dml_store* s, char* out, int32_t cap);
 /* Elementwise shard += src for a dense device buffer of rows*cols values in the
  * store's layout (owner-side apply after a reduce-scatter). */
 int dml_store_apply_dense_device(dml_store* s, const void* dev_src, int64_t elems);
+/* shard = src for a dense device buffer of rows*cols values in the store's
+ * layout, on the store's stream, ordered after every accepted push and before
+ * every later one: the owner's commit of its slice when a chained
+ * reduce-scatter (dml_group_push_chained) brings it home. The slice started
+ * from the shard and every rank added its rows to it one IEEE rounding at a
+ * time, so the assignment leaves what the reference's row[i] += v loops leave
+ * (FloatMatrixStore.java:200-222, DoubleMatrixStore.java:153-190). Plain
+ * dense-column matrices only (f32 / f64 / i32). Earlier pushes are retired
+ * first, so the copy lands in the buffer the last of them wrote (a speculative
+ * batch commits the store's second buffer); dml_store_device_ptr's validity
+ * rule is unchanged. dev_src is read on the store's stream: keep it until that
+ * stream has passed the copy (an event, or dml_store_flush). */
+int dml_store_assign_dense_device(dml_store* s, const void* dev_src, int64_t elems);
 /* Two-moment AdaGrad owner apply: dev_src holds rows x [cols Σu |
  * cols Σu²] f32 (the reduce-scattered dml_prereduce_moments_piece output of the
  * shard's rows); data += Σu, delta += Σu², alpha = initialAlpha / (factor *
@@ -312,6 +325,28 @@ int dml_prereduce_begin(const dml_desc* desc, int64_t first_key, int64_t rows, i
 int dml_prereduce_piece(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
                         int64_t ntask_rows, void* dev_out, void* stream);
 int dml_prereduce_end(dml_prereduce* p);
+/* One step of a chained (ring-ordered) reduce-scatter, for plain fp32 / fp64
+ * matrices: like _piece (same row map, stream rule, host wait for the index
+ * when `stream` differs from _begin's, completion event for _stream_wait,
+ * timing), but task row t starts from dev_base + t*cols instead of zero. The
+ * handle's pushes' records of model row r(t) are added to it in push order,
+ * one IEEE rounding per add, exactly as the store's own push adds them
+ * (FloatMatrixStore.java:200-222, DoubleMatrixStore.java:153-190), and the row
+ * is written to dev_out + t*cols. dev_out == dev_base (in place) is allowed.
+ * A row no push lists is copied bit for bit: it gets no add of +0.0, which
+ * would turn a -0.0 into +0.0. Padding rows (r(t) >= rows) are copied too. A
+ * slice handed from rank to rank through one such piece each therefore holds
+ * what one reference store holds after handlePush of the ranks' pushes in ring
+ * order — an arrival order the reference's server may see (PSAgent.java:166-186).
+ * Nothing unverified is written: a handle with no pushes, or whose index found a
+ * key outside the matrix or a row listed twice in one push, copies dev_base to
+ * dev_out (_end reports the error); ascending full-range pushes of a narrow-row
+ * matrix are checked key by key before the first piece. DML_E_UNSUPPORTED for
+ * int32 and AdaGrad descriptors (use dml_group_push_exchange) and for a handle
+ * begun in a speculative context (dml_prereduce_begin_ctx), whose verdict comes
+ * after the piece has run. */
+int dml_prereduce_chain_piece(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
+                              int64_t ntask_rows, const void* dev_base, void* dev_out, void* stream);
 /* The two-moment piece of an AdaGrad matrix's pre-reduce (begun with its desc):
  * task row t's Σu and Σu·u over the pushes, in push order, written as
  * dev_out + t*2*cols = [cols Σu | cols Σu²] (f32; rows of whole 16-B vectors
@@ -428,6 +463,38 @@ int dml_group_push_moments(dml_group* g, const void* const* dev_bufs, const int6
  * store's exact ordered device push (dml_store_push_batch_device), queued after
  * every earlier group call's apply; no collective. */
 int dml_group_push_local(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n);
+/* Order-exact chained reduce-scatter of the rank's n (0 <= n <= 64; ranks may
+ * differ) full-range pushes, for plain fp32 / fp64 matrices. Owner s's slice
+ * starts as shard s and walks the ring s, s+1, ..., s-1: every rank adds its own
+ * pushes' rows of the slice in push order, one IEEE rounding per add
+ * (dml_prereduce_chain_piece), and forwards it with ncclSend / ncclRecv; the last
+ * hop brings it home and the owner commits it (dml_store_assign_dense_device).
+ * After the call, shard s holds, byte for byte, what one reference store over
+ * shard s's key range holds after handlePush (FloatMatrixStore.java:200-222,
+ * DoubleMatrixStore.java:153-190) of rank s's pushes in push order, then rank
+ * s+1's, ..., then rank s-1's, each restricted to the records whose key lies in
+ * the shard — an arrival order the reference's server may see (it applies pushes
+ * as they arrive, PSAgent.java:166-186). A row a push does not list gets no add
+ * from it (not even of +0.0). Per rank the call moves one model's bytes over
+ * xGMI whatever n is (N-1 of its N slices are other shards'), in `pieces`
+ * sub-chunks per slice, each sent while the next one is summed.
+ * Order: the group's calls (push_local, push_full_range, push_exchange,
+ * push_chained) apply to the store in call order, no flush needed between them.
+ * Pushes as for the other device pushes: 4-byte aligned, read inside
+ * [ptr, ptr + len) only, valid until dml_group_flush.
+ * Failures: argument errors (null or misaligned pointer, n out of range) are
+ * refused before the group's state moves and before the rank joins the ring.
+ * A local failure never changes the sequence of sends and receives: the rank
+ * forwards every slice unchanged in all N steps, its pushes appear in no shard,
+ * and the other ranks' contributions still reach every shard, its own
+ * included. A push that is not whole records, or a HIP error before the
+ * pieces, is returned by this call; a key outside the matrix or a row listed
+ * twice in one push (found by the key index on the device) is returned by the
+ * rank's next group call or by dml_group_flush.
+ * At world 1 the call is dml_store_push_batch_device. int32 and AdaGrad
+ * descriptors: DML_E_UNSUPPORTED (use dml_group_push_exchange), on every rank
+ * alike and before any send. */
+int dml_group_push_chained(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n);
 int dml_group_flush(dml_group* g);
 void dml_group_destroy(dml_group* g);
 /* Fault injection for tests: the nth full-range call finished from now on (1 = the

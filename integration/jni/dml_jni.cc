@@ -326,7 +326,8 @@ JNIEXPORT jlong JNICALL GFN(nativeGroupCreate)(JNIEnv* env, jclass, jbyteArray i
     return reinterpret_cast<jlong>(g);
 }
 
-// mode: 0 full-range pre-reduce, 1 exact exchange, 2 two-moment AdaGrad, 3 local (already split)
+// mode: 0 full-range pre-reduce, 1 exact exchange, 2 two-moment AdaGrad, 3 local (already split),
+// 4 order-exact chained reduce-scatter (fp32 / fp64)
 JNIEXPORT void JNICALL GFN(nativeGroupPush)(JNIEnv* env, jclass, jlong g, jlongArray ptrs, jlongArray lens,
                                              jint mode) {
     const jsize n = env->GetArrayLength(ptrs);
@@ -345,6 +346,7 @@ JNIEXPORT void JNICALL GFN(nativeGroupPush)(JNIEnv* env, jclass, jlong g, jlongA
         case 1: rc = dml_group_push_exchange(G(g), dp.data(), dl.data(), (int32_t)n); break;
         case 2: rc = dml_group_push_moments(G(g), dp.data(), dl.data(), (int32_t)n); break;
         case 3: rc = dml_group_push_local(G(g), dp.data(), dl.data(), (int32_t)n); break;
+        case 4: rc = dml_group_push_chained(G(g), dp.data(), dl.data(), (int32_t)n); break;
         default: break;
     }
     if (rc) throw_for(env, rc);
