@@ -78,11 +78,14 @@ SIGNATURES = {
     "dml_store_kernel_name": (C.c_int, [_vp, C.c_char_p, _i32]),
     "dml_store_apply_dense_device": (C.c_int, [_vp, _vp, _i64]),
     "dml_store_assign_dense_device": (C.c_int, [_vp, _vp, _i64]),
+    "dml_store_assign_adagrad_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "dml_store_apply_adagrad_moments_device": (C.c_int, [_vp, _vp, _i64]),
     "dml_reduce_buckets_dense": (C.c_int, [_P(dml_desc), _i64, _i64, _i32, _P(_vp), _P(_i64), _i32, _vp, _vp]),
     "dml_prereduce_begin": (C.c_int, [_P(dml_desc), _i64, _i64, _i32, _P(_vp), _P(_i64), _i32, _vp, _P(_vp)]),
     "dml_prereduce_piece": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "dml_prereduce_chain_piece": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "dml_prereduce_chain_piece_ada": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                                _vp]),
     "dml_prereduce_end": (C.c_int, [_vp]),
     "dml_prereduce_moments_piece": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "dml_prereduce_stream_wait": (C.c_int, [_vp, _vp]),

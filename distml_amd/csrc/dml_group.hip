@@ -21,8 +21,12 @@
 // channel count pinned, kRsChannels) with a unique id the caller distributes (the
 // JVM's control plane).
 // dml_group_push_chained is the order-exact alternative for plain fp32 / fp64
-// matrices: each shard's slice walks the ring of ranks over ncclSend / ncclRecv and
-// every rank adds its own pushes' rows to it in push order.
+// matrices and for AdaGrad matrices: each shard's slice walks the ring of ranks over
+// ncclSend / ncclRecv and every rank adds its own pushes' rows to it in push order
+// (DESIGN.md §6). An AdaGrad slice carries data, delta, a touched mark per row and
+// the maxDelta record; the owner computes alpha once at its commit. One documented
+// divergence there (the alpha of an element whose delta comes home NaN, DESIGN.md
+// §2); dml_group_push_exchange is the path without it.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -112,8 +116,10 @@ struct dml_group {
     // chained path (dml_group_push_chained), allocated on its first call: two buffer
     // sets by call, each two slice buffers the ring steps alternate between (step t
     // sums in place in the one that step t-1 received into, while the other receives)
+    // (an AdaGrad slice: `pieces` messages of [data rows][delta rows][marks][record], chain_msg)
     void* cbuf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     std::vector<hipEvent_t> cev[2];  // per set: [step][sub-chunk] piece done, then [step][sub-chunk] received
+    void* cmd = nullptr;             // AdaGrad: the running step's pending maxDelta candidate (a MaxDelta)
     hipEvent_t cready = nullptr;     // store stream: every earlier call's apply is enqueued before it
     std::deque<dml_prereduce*> cpending;  // calls whose index errors are not yet collected
     int ck = 0;
@@ -223,6 +229,7 @@ void group_free(dml_group* g) {
     (void)end_chained(g, 0);
     if (g->pctx) dml_prectx_destroy(g->pctx);
     if (g->cready) (void)hipEventDestroy(g->cready);
+    if (g->cmd) (void)hipFree(g->cmd);
     for (int i = 0; i < 2; ++i) {
         for (void* b : g->cbuf[i])
             if (b) (void)hipFree(b);
@@ -623,6 +630,21 @@ int dml_group_push_local(dml_group* g, const void* const* dev_bufs, const int64_
     return dml_store_push_batch_device(g->store, dev_bufs, lens, n);
 }
 
+// An AdaGrad sub-chunk of nr rows as it travels, one contiguous message: [data nr x
+// cols][delta nr x cols][marks nr x uint32], then, 8-byte aligned, the slice's maxDelta
+// record (a whole MaxDelta, DML_MAXDELTA_RECORD_BYTES) on the slice's last sub-chunk.
+struct ChainMsg {
+    size_t delta, marks, rec, wire;  // byte offsets inside the message; bytes sent
+};
+static ChainMsg chain_msg(int64_t nr, size_t rowb, bool with_rec) {
+    ChainMsg m;
+    m.delta = (size_t)nr * rowb;
+    m.marks = 2 * m.delta;
+    m.rec = (m.marks + (size_t)nr * 4 + 7) & ~(size_t)7;
+    m.wire = with_rec ? m.rec + sizeof(MaxDelta) : m.marks + (size_t)nr * 4;
+    return m;
+}
+
 // Order-exact chained reduce-scatter (contract: include/distml_ps.h). At ring step t
 // rank r holds slice q = (r - t) mod N (the rows of shard q): it adds its pushes' rows
 // of q (a chain piece on cstream; step 0 starts from its own shard, later steps sum in
@@ -635,14 +657,22 @@ int dml_group_push_local(dml_group* g, const void* const* dev_bufs, const int64_
 // have run by then, or are waited for), so the host runs one call ahead of the ring.
 // A local failure (first = a code) changes no send and no receive: the rank forwards
 // every slice as it holds it.
+// AdaGrad groups run the same ring with dml_prereduce_chain_piece_ada. The slice's
+// record arrives with its last sub-chunk, so the earlier sub-chunks' pieces collect
+// their maxDelta candidates in the group's own record (cmd, kMdDefer); they are copied
+// into the travelling record once it is there, and the last piece applies them
+// (kMdApply): one strict > per rank against the earlier ranks, whichever piece held
+// the rank's best candidate.
 int dml_group_push_chained(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
     if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
         return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
     if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
     // the same answer on every rank, before any send: nobody waits for a peer
-    if (!g->plain || g->desc.value_type == DML_ELEMENT_TYPE_INT)
+    const bool ada = g->desc.data_type == DML_DATA_TYPE_MATRIX && g->desc.ada_grad &&
+                     g->desc.value_type == DML_ELEMENT_TYPE_FLOAT;
+    if ((!g->plain && !ada) || g->desc.value_type == DML_ELEMENT_TYPE_INT)
         return set_error(DML_E_UNSUPPORTED,
-                         "the chained path sums plain fp32 / fp64 matrices (int32 and AdaGrad: use dml_group_push_exchange)");
+                         "the chained path serves fp32 / fp64 matrices, plain or AdaGrad (int32: use dml_group_push_exchange)");
     GHIP(hipSetDevice(g->device));
     if (g->xheld) {  // an exchange call's slices come first: the store applies calls in order
         GHIP(hipStreamSynchronize(g->rstream));
@@ -660,13 +690,18 @@ int dml_group_push_chained(dml_group* g, const void* const* dev_bufs, const int6
     const size_t rowb = (size_t)C * g->vbytes;
     std::vector<int64_t> f((size_t)W), l((size_t)W);
     GRC(dml_linear_split(0, g->total_rows - 1, W, f.data(), l.data()));
+    // an AdaGrad slice buffer: `pieces` message slots of the longest sub-chunk's size
+    const int64_t per_max = (g->step_rows + P - 1) / P;
+    const size_t mslot = ada ? (chain_msg(per_max, rowb, true).wire + 15) & ~(size_t)15 : 0;
     if (!g->cbuf[0][0]) {  // first chained call: a group that never makes one pays nothing
+        const size_t bytes = ada ? mslot * (size_t)P : (size_t)g->step_rows * rowb;
         for (int i = 0; i < 2; ++i) {
-            for (int j = 0; j < 2; ++j) GHIP(hipMalloc(&g->cbuf[i][j], (size_t)g->step_rows * rowb));
+            for (int j = 0; j < 2; ++j) GHIP(hipMalloc(&g->cbuf[i][j], bytes));
             g->cev[i].resize((size_t)2 * W * P, nullptr);
             for (hipEvent_t& e : g->cev[i]) GHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
         GHIP(hipEventCreateWithFlags(&g->cready, hipEventDisableTiming));
+        if (ada) GHIP(hipMalloc(&g->cmd, sizeof(MaxDelta)));
     }
     const int set = g->ck;
     g->ck ^= 1;
@@ -685,10 +720,13 @@ int dml_group_push_chained(dml_group* g, const void* const* dev_bufs, const int6
     // value pointer is then current) and cstream waits for what the store's stream holds
     uint64_t seq = 0;
     void* shard = nullptr;
+    float* sdelta = nullptr;
+    void* smd = nullptr;
     int rs = dml_store_push_seq(g->store, &seq);
     if (rs == DML_OK) rs = dml_store_retire(g->store, seq);
     note(rs);
     GRC(dml_store_device_ptr(g->store, &shard));
+    if (ada) GRC(store_adagrad_ptrs(g->store, &sdelta, &smd));
     hip(hipEventRecord(g->cready, g->sstream), "hipEventRecord");
     hip(hipStreamWaitEvent(g->cstream, g->cready, 0), "hipStreamWaitEvent");
     uint8_t* const B[2] = {(uint8_t*)g->cbuf[set][0], (uint8_t*)g->cbuf[set][1]};
@@ -702,30 +740,70 @@ int dml_group_push_chained(dml_group* g, const void* const* dev_bufs, const int6
         *r0 = std::min<int64_t>((int64_t)k * per, rows);
         *nr = std::min<int64_t>(per, rows - *r0);
     };
+    constexpr size_t kRecHead = offsetof(MaxDelta, pend);  // value, row, col
+    if (ada) {
+        // the travelling record of the rank's own slice starts as the store's running
+        // maxDelta, with no pending candidate
+        int64_t r0, nr;
+        sub(g->rank, P - 1, &r0, &nr);
+        uint8_t* const rec = B[0] + (size_t)(P - 1) * mslot + chain_msg(nr, rowb, true).rec;
+        hip(hipMemcpyAsync(rec, smd, kRecHead, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+        hip(hipMemsetAsync(rec + kRecHead, 0, sizeof(MaxDelta) - kRecHead, g->cstream), "hipMemsetAsync");
+    }
     for (int t = 0; t < W; ++t) {
         const int q = (g->rank - t + W) % W, qin = (q + W - 1) % W;
         uint8_t* const cur = B[t & 1];        // step t's slice (t > 0: arrived here in step t - 1)
         uint8_t* const in = B[(t + 1) & 1];   // slice qin lands here
+        if (ada && P > 1 && first == DML_OK)  // this step's candidates start from none
+            hip(hipMemsetAsync(g->cmd, 0, sizeof(MaxDelta), g->cstream), "hipMemsetAsync");
         for (int k = 0; k < P; ++k) {
             int64_t r0, nr, i0, ni;
             sub(q, k, &r0, &nr);
             sub(qin, k, &i0, &ni);
-            uint8_t* const out = cur + (size_t)r0 * rowb;
-            if (nr > 0) {
+            const bool lastk = k == P - 1;
+            uint8_t* const out = ada ? cur + (size_t)k * mslot : cur + (size_t)r0 * rowb;
+            uint8_t* const land = ada ? in + (size_t)k * mslot : in + (size_t)i0 * rowb;
+            const ChainMsg mo = chain_msg(nr, rowb, lastk), mi = chain_msg(ni, rowb, lastk);
+            if (nr > 0 || (ada && lastk)) {
                 const uint8_t* const base = t == 0 ? (const uint8_t*)shard + (size_t)r0 * rowb : out;
                 if (t > 0) hip(hipStreamWaitEvent(g->cstream, rdone[(t - 1) * P + k], 0), "hipStreamWaitEvent");
-                if (first == DML_OK)
-                    note(dml_prereduce_chain_piece(h, nr, nr, f[(size_t)q] + r0, nr, base, out, g->cstream));
-                // a failed rank forwards the slice as it holds it (step 0: its own shard's rows)
-                if (first != DML_OK && t == 0)
-                    hip(hipMemcpyAsync(out, base, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+                if (ada) {
+                    const uint8_t* const bdl = t == 0 ? (const uint8_t*)sdelta + (size_t)r0 * rowb : out + mo.delta;
+                    // the slice's record sits in its last sub-chunk's slot
+                    int64_t lr0, lnr;
+                    sub(q, P - 1, &lr0, &lnr);
+                    uint8_t* const rec = cur + (size_t)(P - 1) * mslot + chain_msg(lnr, rowb, true).rec;
+                    if (first == DML_OK && lastk && P > 1)
+                        hip(hipMemcpyAsync(rec + kRecHead, (const uint8_t*)g->cmd + kRecHead, sizeof(MaxDelta) - kRecHead,
+                                           hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+                    if (first == DML_OK)
+                        note(dml_prereduce_chain_piece_ada(h, std::max<int64_t>(nr, 1), std::max<int64_t>(nr, 1),
+                                                           f[(size_t)q] + r0, nr, base, bdl,
+                                                           t == 0 ? nullptr : out + mo.marks, out, out + mo.delta,
+                                                           out + mo.marks, lastk ? (void*)rec : g->cmd, lastk ? 1 : 0, g->cstream));
+                    // a failed rank forwards the slice as it holds it (step 0: its own shard's planes,
+                    // clear marks, the store's record, which is in place already)
+                    if (first != DML_OK && t == 0 && nr > 0) {
+                        hip(hipMemcpyAsync(out, base, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+                        hip(hipMemcpyAsync(out + mo.delta, bdl, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream),
+                            "hipMemcpyAsync");
+                        hip(hipMemsetAsync(out + mo.marks, 0, (size_t)nr * 4, g->cstream), "hipMemsetAsync");
+                    }
+                } else {
+                    if (first == DML_OK)
+                        note(dml_prereduce_chain_piece(h, nr, nr, f[(size_t)q] + r0, nr, base, out, g->cstream));
+                    // a failed rank forwards the slice as it holds it (step 0: its own shard's rows)
+                    if (first != DML_OK && t == 0)
+                        hip(hipMemcpyAsync(out, base, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+                }
                 hip(hipEventRecord(pdone[t * P + k], g->cstream), "hipEventRecord");
                 hip(hipStreamWaitEvent(g->rstream, pdone[t * P + k], 0), "hipStreamWaitEvent");
             }
             // every rank issues this group, empty sub-chunks included (zero bytes)
+            const size_t sbytes = ada ? mo.wire : (size_t)nr * rowb, rbytes = ada ? mi.wire : (size_t)ni * rowb;
             ncclResult_t r = ncclGroupStart();
-            if (r == ncclSuccess) r = ncclSend(out, (size_t)nr * rowb, ncclUint8, nxt, g->comm, g->rstream);
-            if (r == ncclSuccess) r = ncclRecv(in + (size_t)i0 * rowb, (size_t)ni * rowb, ncclUint8, prv, g->comm, g->rstream);
+            if (r == ncclSuccess) r = ncclSend(out, sbytes, ncclUint8, nxt, g->comm, g->rstream);
+            if (r == ncclSuccess) r = ncclRecv(land, rbytes, ncclUint8, prv, g->comm, g->rstream);
             const ncclResult_t re = ncclGroupEnd();
             if (r == ncclSuccess) r = re;
             if (r != ncclSuccess && crc == DML_OK)
@@ -736,7 +814,19 @@ int dml_group_push_chained(dml_group* g, const void* const* dev_bufs, const int6
     // home: step N-1 received the rank's own slice, every rank's adds in it
     hip(hipStreamWaitEvent(g->sstream, rdone[(W - 1) * P + P - 1], 0), "hipStreamWaitEvent");
     int commit = crc;
-    if (commit == DML_OK) commit = dml_store_assign_dense_device(g->store, B[W & 1], g->shard_rows * C);
+    if (commit == DML_OK && !ada) commit = dml_store_assign_dense_device(g->store, B[W & 1], g->shard_rows * C);
+    if (commit == DML_OK && ada) {
+        const uint8_t* const home = B[W & 1];
+        for (int k = 0; k < P && commit == DML_OK; ++k) {
+            int64_t r0, nr;
+            sub(g->rank, k, &r0, &nr);
+            const ChainMsg m = chain_msg(nr, rowb, k == P - 1);
+            const uint8_t* const msg = home + (size_t)k * mslot;
+            if (nr > 0 || k == P - 1)
+                commit = store_assign_adagrad(g->store, r0, nr, msg, msg + m.delta, msg + m.marks,
+                                              k == P - 1 ? msg + m.rec : nullptr);
+        }
+    }
     if (h) g->cpending.push_back(h);
     const int older = end_chained(g, 1);  // the previous chained call's key / repeated-row errors
     return prior != DML_OK ? prior : first != DML_OK ? first : commit != DML_OK ? commit : older;

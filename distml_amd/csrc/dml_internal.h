@@ -6,6 +6,8 @@
 
 #include <string>
 
+struct dml_store;
+
 namespace dml {
 
 // One ordered batch chunk holds at most this many pushes (the slot table is
@@ -118,6 +120,7 @@ struct MaxDelta {
     int32_t pad;
     DeltaCand pend;
 };
+static_assert(sizeof(MaxDelta) == 32, "MaxDelta layout (DML_MAXDELTA_RECORD_BYTES: a chained AdaGrad slice carries one)");
 // k_maxdelta finalize modes
 enum MdMode : int {
     kMdApply = 0,          // merge with the pending candidate, apply (strict >), clear it
@@ -311,6 +314,29 @@ hipError_t launch_moments(int64_t ntask, int32_t cols, const Batch& bt, int nb, 
 hipError_t launch_ada_moments(float* shard, const float* src, int64_t rows, int32_t cols, const AdaArgs& ada,
                               MaxDelta* md, int64_t first, hipStream_t st, LaunchEv ev);
 
+// Chained reduce-scatter step of an AdaGrad matrix: the planes beside
+// RowMap::base / RowMap::out (data). Marks: one uint32 per task row, non-zero = some
+// rank's accepted push listed the row in this call; base_marks == null reads as all
+// clear (ring step 0).
+struct ChainAda {
+    const float* base_delta;
+    float* out_delta;
+    const uint32_t* base_marks;
+    uint32_t* out_marks;
+    DeltaCand* cand;  // one per block (chain_ada_blocks)
+};
+// ident: k_chain_ada_ident (every push confirmed identity by k_ident_full, rows of
+// whole 16-B vectors); otherwise k_chain_ada_rows over the slot table.
+int64_t chain_ada_blocks(bool ident, int64_t ntask, int32_t cols);
+hipError_t launch_chain_ada(bool ident, int64_t ntask, int32_t cols, const Batch& bt, int nb, int64_t stride, int K,
+                            int32_t* slot, const Ctrl* ctrl, RowMap rm, const ChainAda& ca, hipStream_t st,
+                            int64_t* ncand_out, LaunchEv ev);
+// The owner's commit of the slice that came home: data, delta, alpha where marked and
+// delta > 1 (ada's parameters), and the running maxDelta = *rec.
+hipError_t launch_chain_ada_commit(float* data, float* delta, float* alpha, MaxDelta* md, const float* sdata,
+                                   const float* sdelta, const uint32_t* marks, const MaxDelta* rec, int64_t rows,
+                                   int32_t cols, const AdaArgs& ada, hipStream_t st);
+
 hipError_t launch_stream(bool copy, void* dst, const void* src, int64_t n16, hipStream_t st, LaunchEv ev);
 hipError_t launch_rmw_floor(float* a, const uint32_t* idx, const float* v, int64_t n, hipStream_t st, LaunchEv ev);
 hipError_t launch_dense_floor(const float* data, float* out, float* delta, const Batch& bt, int nb, int64_t stride,
@@ -376,5 +402,11 @@ inline const char* type_name() {
 // Records `msg` as the calling thread's dml_last_error() and returns `code`
 // (dml_store.hip; shared by the C-ABI translation units).
 int set_error(int code, const std::string& msg);
+// The store's side of a chained AdaGrad call, for the group (dml_store.hip): the commit
+// of rows [row0, row0 + nrows) of the slice that came home (rec == null: the running
+// maxDelta stays), and the device addresses of the delta plane and the running MaxDelta.
+int store_assign_adagrad(dml_store* s, int64_t row0, int64_t nrows, const void* data, const void* delta,
+                         const void* marks, const void* rec);
+int store_adagrad_ptrs(dml_store* s, float** delta, void** maxdelta);
 
 }  // namespace dml

@@ -13,6 +13,11 @@
 //   k_array_rollback int32 array stores: undo every add after the first negative
 //                   counter (IntArrayStore.java:97-113); the arrays' ordered
 //                   scatter-add itself is the partition + leaf path of dml_sparse.hip
+//   k_chain_ada_ident, k_chain_ada_rows, k_chain_ada_commit  the chained
+//                   reduce-scatter's step and owner commit for AdaGrad matrices
+//                   (data + delta planes, touched marks, maxDelta candidates; one
+//                   documented divergence, the alpha of an element whose delta comes
+//                   home NaN — dml_group_push_exchange is the path without it)
 //   k_fetch, k_bswap, k_fill, k_apply_dense, k_synth_*  — fetch / checkpoint /
 //                   init / owner-apply / synthetic data.
 #include "dml_device.h"
@@ -2913,6 +2918,277 @@ hipError_t launch_ada_moments(float* shard, const float* src, int64_t rows, int3
     else
         hipLaunchKernelGGL(k_ada_moments, dim3(kMomentBlocks), dim3(256), 0, st, shard, src, rows, cols, ada);
     hipLaunchKernelGGL(k_maxdelta_elems, dim3(1), dim3(256), 0, st, ada.cand, (int64_t)kMomentBlocks, md, first, cols);
+    return hipGetLastError();
+}
+
+
+// ---------------------------------------------------------------------------
+// Chained reduce-scatter step of an AdaGrad matrix (dml_prereduce_chain_piece_ada,
+// DESIGN.md §6): the slice travels as two planes, data and delta, plus one 4-byte
+// touched mark per row. Task row t starts from base + t*cols in both planes; the
+// handle's pushes' records of its model row are added in push order with the
+// arithmetic of k_ada_ident / k_ada_flat (acc = acc + g, nd = dl + g*g, one IEEE
+// rounding each), and both planes are written to the outputs (out == base works:
+// every element and every mark is read and written by one lane). All pushes of the
+// handle (up to 64) go through one pass: the planes are read once and written once
+// whatever the push count, D push loads in flight per lane. No alpha is read or
+// written: the owner computes it once from the delta that comes home
+// (k_chain_ada_commit). An element's last strict rise of delta is its maxDelta
+// candidate, reduced per block (max value, then lowest position) into ca.cand; a
+// handle's pushes are numbered by column (dml_prereduce_begin: bidx[j] = j), so a
+// candidate's position is formed from its push column. A row no push lists, a
+// padding row, and every row of a handle whose index failed (ctrl_index_failed,
+// read by every wave) are copied bit for bit, marks included; a listed row of a
+// good handle sets its mark.
+//
+// k_chain_ada_ident: the vector stream for calls the host has seen to be all
+// identity (ascending full-range pushes of a flat width, every key checked by
+// k_ident_full before the first piece: config 4's shape). A thread owns one 16-B
+// vector of the task planes; its model row goes through the row map per vector, so
+// row blocks of any size work.
+template <int D>
+__global__ __launch_bounds__(256) void k_chain_ada_ident(int64_t nvec, int32_t cols, const Batch bt, int nb,
+                                                         int64_t stride, int K, const Ctrl* __restrict__ ctrl,
+                                                         RowMap rm, ChainAda ca) {
+    constexpr int VEC = 4;
+    const int64_t v = xcd_block() * 256 + threadIdx.x;
+    const bool on = v < nvec;
+    const int64_t e0 = on ? v * VEC : 0;
+    const int64_t t = e0 / cols;
+    const int c = (int)(e0 - t * cols);
+    const int64_t mr = rm.row(t);
+    const bool live = on && mr < rm.rows_total && !ctrl_index_failed(ctrl);
+    const int64_t roff = mr * stride + K + (int64_t)c * 4;
+    const u32x4 z{0u, 0u, 0u, 0u};
+    float acc[VEC], dl[VEC], rv[VEC];
+    int rb[VEC];  // push of the element's last strict rise (-1: none)
+    unpack<float>(on ? ldg16_nt((const uint8_t*)rm.base + e0 * 4) : z, acc);
+    unpack<float>(on ? ldg16_nt((const uint8_t*)ca.base_delta + e0 * 4) : z, dl);
+    uint32_t mark = 0u;
+    if (on && c == 0 && ca.base_marks) mark = ca.base_marks[t];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        rv[e] = 0.f;
+        rb[e] = -1;
+    }
+#pragma unroll 1
+    for (int b0 = 0; b0 < nb; b0 += D) {
+        u32x4 raw[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const int b = b0 + d < nb ? b0 + d : b0;
+            raw[d] = live && b0 + d < nb ? ldg16_nt(bt.base[b] + roff) : z;
+        }
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            if (b0 + d >= nb || !live) continue;
+            float g[VEC];
+            unpack<float>(raw[d], g);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                acc[e] = __fadd_rn(acc[e], g[e]);
+                const float nd = __fadd_rn(dl[e], __fmul_rn(g[e], g[e]));
+                if (nd > dl[e]) { rv[e] = nd; rb[e] = b0 + d; }
+                dl[e] = nd;
+            }
+        }
+    }
+    float cand_v = 0.f;
+    uint64_t cand_p = kNoPos;
+    bool cand_ok = false;
+    if (on) {
+        stg16_nt((uint8_t*)rm.out + e0 * 4, pack<float>(acc));
+        stg16_nt((uint8_t*)ca.out_delta + e0 * 4, pack<float>(dl));
+        if (c == 0) ca.out_marks[t] = live ? 1u : mark;
+        // (push, element) order is position order inside the thread's vector
+        int key = 0;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            if (rb[e] < 0) continue;
+            const int k = (rb[e] << 2) | e;
+            if (!cand_ok || rv[e] > cand_v || (rv[e] == cand_v && k < key)) {
+                cand_ok = true;
+                cand_v = rv[e];
+                key = k;
+            }
+        }
+        if (cand_ok) cand_p = pos_of((uint64_t)(key >> 2), (uint64_t)(roff + (key & 3) * 4));
+    }
+    cand_block_best<4>(cand_ok, cand_v, cand_p);
+    if (threadIdx.x == 0) {
+        DeltaCand cd;
+        cd.value = cand_v;
+        cd.valid = cand_ok;
+        cd.pos = cand_p;
+        ca.cand[blockIdx.x] = cd;
+    }
+}
+
+// k_chain_ada_rows: the slot-table shape for everything else (permuted pushes, ragged
+// or narrow rows, rows no push lists): one wave per task row, its lanes over the
+// row's columns 64 at a time, element by element (any width, 4-byte aligned records).
+// The row's slots (one per push; slot = row for a push k_ident_full confirmed) are
+// read once into LDS and handed back clean (-1), as the pre-reduce kernels do.
+template <int D>
+__global__ __launch_bounds__(256) void k_chain_ada_rows(int64_t ntask, int32_t cols, const Batch bt, int nb,
+                                                        int64_t stride, int K, int32_t* __restrict__ slot,
+                                                        const Ctrl* __restrict__ ctrl, RowMap rm, ChainAda ca) {
+    __shared__ int32_t s_slot[4][kMaxW];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t t = (int64_t)blockIdx.x * 4 + wid;
+    const bool on = t < ntask;
+    const int64_t mr = on ? rm.row(t) : 0;
+    const bool good = on && mr < rm.rows_total && !ctrl_index_failed(ctrl);
+    const uint64_t ident = bt.ident_ok ? ctrl->ident : 0ull;
+    const int ss = slot_stride(nb);
+    int32_t* const ls = s_slot[wid];
+    int32_t sl = -1;
+    if (good && lane < nb) {
+        if ((ident >> lane) & 1ull) {
+            sl = (int32_t)mr;  // a confirmed push is full-range: record r is row r
+        } else {
+            sl = slot[mr * ss + lane];
+            if (sl >= 0) slot[mr * ss + lane] = -1;
+        }
+    }
+    ls[lane] = sl;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const bool live = __ballot(sl >= 0) != 0ull;  // some push lists the row
+    float cand_v = 0.f;
+    uint64_t cand_p = kNoPos;
+    bool cand_ok = false;
+    const float* const bd = (const float*)rm.base;
+    float* const od = (float*)rm.out;
+    for (int c0 = 0; c0 < cols; c0 += 64) {
+        const int c = c0 + lane;
+        const bool act = on && c < cols;
+        const int64_t i = act ? t * (int64_t)cols + c : 0;
+        float acc = 0.f, dl = 0.f, rv = 0.f;
+        int rb = -1;
+        if (act) {
+            acc = bd[i];
+            dl = ca.base_delta[i];
+        }
+        if (live) {
+#pragma unroll 1
+            for (int b0 = 0; b0 < nb; b0 += D) {
+                int32_t s[D];
+                float g[D];
+#pragma unroll
+                for (int d = 0; d < D; ++d) {
+                    const int b = b0 + d < nb ? b0 + d : b0;
+                    s[d] = b0 + d < nb ? __builtin_amdgcn_readfirstlane(ls[b]) : -1;
+                    g[d] = act && s[d] >= 0
+                               ? Elem<float>::load(bt.base[b] + (int64_t)s[d] * stride + K + (int64_t)c * 4)
+                               : 0.f;
+                }
+#pragma unroll
+                for (int d = 0; d < D; ++d) {
+                    if (s[d] < 0 || !act) continue;
+                    acc = __fadd_rn(acc, g[d]);
+                    const float nd = __fadd_rn(dl, __fmul_rn(g[d], g[d]));
+                    if (nd > dl) { rv = nd; rb = b0 + d; }
+                    dl = nd;
+                }
+            }
+        }
+        if (act) {
+            od[i] = acc;
+            ca.out_delta[i] = dl;
+            if (rb >= 0) {
+                const uint64_t p = pos_of((uint64_t)rb, (uint64_t)((int64_t)ls[rb] * stride + K + (int64_t)c * 4));
+                if (cand_better(true, rv, p, cand_ok, cand_v, cand_p)) {
+                    cand_ok = true;
+                    cand_v = rv;
+                    cand_p = p;
+                }
+            }
+        }
+    }
+    if (on && lane == 0) ca.out_marks[t] = live ? 1u : (ca.base_marks ? ca.base_marks[t] : 0u);
+    cand_block_best<4>(cand_ok, cand_v, cand_p);
+    if (threadIdx.x == 0) {
+        DeltaCand cd;
+        cd.value = cand_v;
+        cd.valid = cand_ok;
+        cd.pos = cand_p;
+        ca.cand[blockIdx.x] = cd;
+    }
+}
+
+constexpr int kChainAdaD = 8;  // push loads in flight per lane
+
+int64_t chain_ada_blocks(bool ident, int64_t ntask, int32_t cols) {
+    return ident ? (ntask * (cols / 4) + 255) / 256 : (ntask + 3) / 4;
+}
+
+hipError_t launch_chain_ada(bool ident, int64_t ntask, int32_t cols, const Batch& bt, int nb, int64_t stride, int K,
+                            int32_t* slot, const Ctrl* ctrl, RowMap rm, const ChainAda& ca, hipStream_t st,
+                            int64_t* ncand_out, LaunchEv ev) {
+    if (!rm.base || !rm.out || !ca.base_delta || !ca.out_delta || !ca.out_marks || !ca.cand)
+        return hipErrorInvalidValue;
+    if (ident && (cols % 4 || nb <= 0)) return hipErrorInvalidValue;
+    const int64_t nblocks = chain_ada_blocks(ident, ntask, cols);
+    if (ncand_out) *ncand_out = nblocks;
+    if (nblocks <= 0) return hipSuccess;
+    if (nblocks > INT32_MAX) return hipErrorInvalidValue;
+    constexpr int D = kChainAdaD;
+    if (ident) {
+        static const std::string kn = kname("k_chain_ada_ident", D);
+        g_kernel_name = kn.c_str();
+        hipExtLaunchKernelGGL((k_chain_ada_ident<D>), dim3((unsigned)nblocks), dim3(256), 0, st, ev.start, ev.stop, 0,
+                              ntask * (cols / 4), cols, bt, nb, stride, K, ctrl, rm, ca);
+    } else {
+        static const std::string kn = kname("k_chain_ada_rows", D);
+        g_kernel_name = kn.c_str();
+        hipExtLaunchKernelGGL((k_chain_ada_rows<D>), dim3((unsigned)nblocks), dim3(256), 0, st, ev.start, ev.stop, 0,
+                              ntask, cols, bt, nb, stride, K, slot, ctrl, rm, ca);
+    }
+    return hipGetLastError();
+}
+
+// The owner's commit of its AdaGrad slice when the chain brings it home: shard data
+// and delta = the slice's; alpha = initialAlpha / (factor * sqrt(delta)), clamped to
+// minAlpha (k_ada_ident's expression, the owner's parameters), where the row's mark is
+// set and delta > 1 — inside one call delta never falls, so this is the alpha the
+// reference's last update of the element left (FloatMatrixStoreAdaGrad.java:268-272).
+// A NaN delta fails the comparison: such an element keeps the alpha the owner held
+// (the one documented divergence). The store's running maxDelta
+// becomes the travelling record.
+__global__ __launch_bounds__(256) void k_chain_ada_commit(float* __restrict__ data, float* __restrict__ delta,
+                                                          float* __restrict__ alpha, MaxDelta* __restrict__ md,
+                                                          const float* __restrict__ sdata,
+                                                          const float* __restrict__ sdelta,
+                                                          const uint32_t* __restrict__ marks,
+                                                          const MaxDelta* __restrict__ rec, int64_t n, int32_t cols,
+                                                          float initial_alpha, float min_alpha, float factor) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float d = sdelta[i];
+        data[i] = sdata[i];
+        delta[i] = d;
+        if (d > 1.0f && marks[i / cols] != 0u) {
+            float a = (float)((double)initial_alpha / ((double)factor * sqrt((double)d)));
+            if (a < min_alpha) a = min_alpha;
+            alpha[i] = a;
+        }
+    }
+    if (md && blockIdx.x == 0 && threadIdx.x == 0) {
+        md->value = rec->value;
+        md->row = rec->row;
+        md->col = rec->col;
+    }
+}
+
+hipError_t launch_chain_ada_commit(float* data, float* delta, float* alpha, MaxDelta* md, const float* sdata,
+                                   const float* sdelta, const uint32_t* marks, const MaxDelta* rec, int64_t rows,
+                                   int32_t cols, const AdaArgs& ada, hipStream_t st) {
+    const int64_t n = rows * cols;
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192));
+    hipLaunchKernelGGL(k_chain_ada_commit, dim3(grid), dim3(256), 0, st, data, delta, alpha, md, sdata, sdelta, marks,
+                       rec, n, cols, ada.initial_alpha, ada.min_alpha, ada.factor);
     return hipGetLastError();
 }
 

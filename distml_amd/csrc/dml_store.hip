@@ -1045,6 +1045,38 @@ int begin_call(dml_store* s) {
 
 }  // namespace
 
+// The owner's commit of a chained AdaGrad slice, rows [row0, row0 + nrows) of the shard
+// (dml_store_assign_adagrad_device is the whole shard; the group commits a slice sub-chunk
+// by sub-chunk, as it travelled). rec == null leaves the running maxDelta alone.
+namespace dml {
+int store_assign_adagrad(dml_store* s, int64_t row0, int64_t nrows, const void* data, const void* delta,
+                         const void* marks, const void* rec) {
+    if (int rc = check_store(s)) return rc;
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceGuard g(s->device);
+    if (!s->adagrad) return set_err(DML_E_UNSUPPORTED, "not an AdaGrad store");
+    if (row0 < 0 || nrows < 0 || row0 > s->rows || nrows > s->rows - row0)
+        return set_err(DML_E_INVALID_ARG, "assign: bad row range");
+    // every accepted push is retired first, as in dml_store_assign_dense_device
+    if (int rc = retire_all(s)) return rc;
+    if (s->err) return set_err(s->err, "store is in a failed state (see dml_store_error_state)");
+    if (nrows == 0 && !rec) return DML_OK;
+    const int64_t e0 = row0 * s->cols;
+    HIPCHK(launch_chain_ada_commit((float*)s->data + e0, s->delta + e0, s->alpha + e0, rec ? s->md : nullptr,
+                                   (const float*)data, (const float*)delta, (const uint32_t*)marks,
+                                   (const MaxDelta*)rec, nrows, s->cols, ada_args(s), s->stream));
+    return DML_OK;
+}
+
+int store_adagrad_ptrs(dml_store* s, float** delta, void** maxdelta) {
+    if (int rc = check_store(s)) return rc;
+    if (!s->adagrad) return set_err(DML_E_UNSUPPORTED, "not an AdaGrad store");
+    *delta = s->delta;
+    *maxdelta = s->md;
+    return DML_OK;
+}
+}  // namespace dml
+
 // ===========================================================================
 extern "C" {
 
@@ -1748,6 +1780,14 @@ int dml_store_assign_dense_device(dml_store* s, const void* dev_src, int64_t ele
     return DML_OK;
 }
 
+int dml_store_assign_adagrad_device(dml_store* s, const void* dev_data, const void* dev_delta, const void* dev_marks,
+                                    const void* dev_maxdelta_record) {
+    if (int rc = check_store(s)) return rc;
+    if (!dev_data || !dev_delta || !dev_marks || !dev_maxdelta_record)
+        return set_err(DML_E_INVALID_ARG, "assign: null plane or record");
+    return store_assign_adagrad(s, 0, s->rows, dev_data, dev_delta, dev_marks, dev_maxdelta_record);
+}
+
 int dml_store_apply_adagrad_moments_device(dml_store* s, const void* dev_src, int64_t rows) {
     if (int rc = check_store(s)) return rc;
     std::lock_guard<std::mutex> lk(s->mu);
@@ -1818,6 +1858,39 @@ static void ws_release(int dev, const WsLease& l) {
     if (!l.ptr) return;
     std::lock_guard<std::mutex> lk(g_ws_mu);
     g_ws_free[dev].push_back(l);
+}
+
+// Per-device pool of maxDelta candidate buffers for the AdaGrad chain pieces
+// (dml_prereduce_chain_piece_ada): n candidates plus the finalize's kMdParts of
+// scratch, taken and returned like the workspaces.
+struct CandBuf {
+    DeltaCand* ptr = nullptr;
+    int64_t n = 0;
+};
+static std::unordered_map<int, std::vector<CandBuf>> g_cand_free;
+
+static int cand_acquire(int dev, int64_t n, CandBuf* out) {
+    {
+        std::lock_guard<std::mutex> lk(g_ws_mu);
+        auto& v = g_cand_free[dev];
+        for (size_t i = 0; i < v.size(); ++i)
+            if (v[i].n >= n) {
+                *out = v[i];
+                v.erase(v.begin() + (ptrdiff_t)i);
+                return DML_OK;
+            }
+    }
+    CandBuf b;
+    HIPCHK(hipMalloc((void**)&b.ptr, sizeof(DeltaCand) * (size_t)(n + kMdParts)));
+    b.n = n;
+    *out = b;
+    return DML_OK;
+}
+
+static void cand_release(int dev, const std::vector<CandBuf>& bufs) {
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    for (const CandBuf& b : bufs)
+        if (b.ptr) g_cand_free[dev].push_back(b);
 }
 
 extern "C" {
@@ -1921,6 +1994,7 @@ struct dml_prereduce {
     const Ctrl* hidx = nullptr;  // the workspace's Ctrl as the index left it (speculative calls of the flat shape)
     bool chain_checked = false;  // the first chain piece decided about the up-front identity check
     bool slots_unread = false;   // that check ran after the index: the pieces leave the filled slot table as it is
+    std::vector<CandBuf> cands;  // AdaGrad chain pieces: maxDelta candidates (the last is current), back to the pool at _end
 };
 
 // Pre-reduce context (dml_prectx_*): the sharded path's pre-reduce with the
@@ -2176,8 +2250,17 @@ int dml_prereduce_moments_piece(dml_prereduce* p, int64_t row_block, int64_t row
 // One piece of a pre-reduce handle: `mode` kPreReduce (dml_prereduce_piece: sums from
 // zero) or kChain (dml_prereduce_chain_piece: sums onto dev_base, a chained
 // reduce-scatter step). Row map, stream rule, completion event and timing are shared.
+struct AdaPiece {
+    const void* base_delta;
+    const void* base_marks;
+    void* out_delta;
+    void* out_marks;
+    void* record;  // the slice's travelling MaxDelta
+    bool last;     // last piece of this rank's step over the slice
+};
 static int prereduce_piece(dml_prereduce* p, int mode, int64_t row_block, int64_t row_stride, int64_t row_off,
-                           int64_t ntask_rows, const void* dev_base, void* dev_out, void* stream) {
+                           int64_t ntask_rows, const void* dev_base, void* dev_out, void* stream,
+                           const AdaPiece* ap = nullptr) {
     hipStream_t st = (hipStream_t)stream;  // as given: 0 is HIP's null stream
     if (mode == kChain && !p->chain_checked) {
         // Ascending full-range pushes of a flat shape (config 4's case): verify every
@@ -2217,6 +2300,7 @@ static int prereduce_piece(dml_prereduce* p, int mode, int64_t row_block, int64_
     if (!p->last_ev) HIPCHK(hipEventCreateWithFlags(&p->last_ev, hipEventDisableTiming));
     // the piece's completion event rides in its dispatch packet (no marker packet between pieces)
     LaunchEv ev{nullptr, p->last_ev};
+    if (ap) ev.stop = nullptr;  // the candidates' finalize follows the kernel: last_ev is recorded behind it
     if (p->timed) {
         std::pair<hipEvent_t, hipEvent_t> t{nullptr, nullptr};
         {
@@ -2236,7 +2320,27 @@ static int prereduce_piece(dml_prereduce* p, int mode, int64_t row_block, int64_
     // all-identity calls (seen in the index's Ctrl, once the host has waited for it):
     // the lean kernel, when no wave's rows straddle two row blocks of the map
     const int Rw = flat_ident_rows_per_wave(p->desc.value_type, p->cols);
-    if (p->hidx && p->idx_waited && (row_block % Rw == 0 || ntask_rows <= row_block) &&
+    if (ap) {
+        // the vector stream needs no whole waves per row block (its row map is per vector)
+        const bool ident = p->hidx && p->idx_waited && flat_ident_ok(*p->hidx, p->bt, p->nb, p->rows, kNoPos);
+        const int64_t need = std::max<int64_t>(1, chain_ada_blocks(ident, ntask_rows, p->cols));
+        if (p->cands.empty() || p->cands.back().n < need) {
+            CandBuf cb;
+            if (int rc = cand_acquire(p->device, need, &cb)) return rc;
+            p->cands.push_back(cb);
+        }
+        ChainAda ca{(const float*)ap->base_delta, (float*)ap->out_delta, (const uint32_t*)ap->base_marks,
+                    (uint32_t*)ap->out_marks, p->cands.back().ptr};
+        int64_t ncand = 0;
+        HIPCHK(launch_chain_ada(ident, ntask_rows, p->cols, p->bt, p->nb, p->stride, p->K, p->slot, p->ctrl, rm, ca, st,
+                                &ncand, ev));
+        // this piece's candidates into the record's pending one; the step's last piece applies
+        // the strict > against the earlier ranks once (ties inside the rank: earlier position)
+        HIPCHK(launch_maxdelta_finalize(ca.cand, ncand, (MaxDelta*)ap->record, p->bt, p->nb, p->stride, p->K, p->V, st,
+                                        ap->last ? kMdApply : kMdDefer));
+        HIPCHK(hipEventRecord(p->last_ev, st));
+        ev.stop = p->last_ev;
+    } else if (p->hidx && p->idx_waited && (row_block % Rw == 0 || ntask_rows <= row_block) &&
         flat_ident_ok(*p->hidx, p->bt, p->nb, p->rows, kNoPos)) {
         if (p->ctx) {
             std::lock_guard<std::mutex> lk(p->ctx->mu);
@@ -2279,6 +2383,22 @@ int dml_prereduce_chain_piece(dml_prereduce* p, int64_t row_block, int64_t row_s
     // (dml_prereduce_verify) would come after the slice has left the rank
     if (p->ctx) return set_err(DML_E_UNSUPPORTED, "chained pieces need dml_prereduce_begin (no speculative context)");
     return prereduce_piece(p, kChain, row_block, row_stride, row_off, ntask_rows, dev_base, dev_out, stream);
+}
+
+int dml_prereduce_chain_piece_ada(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
+                                  int64_t ntask_rows, const void* base_data, const void* base_delta,
+                                  const void* base_marks, void* out_data, void* out_delta, void* out_marks,
+                                  void* maxdelta_record, int32_t last_piece, void* stream) {
+    if (!p || !base_data || !base_delta || !out_data || !out_delta || !out_marks || !maxdelta_record || row_block <= 0 ||
+        ntask_rows < 0)
+        return set_err(DML_E_INVALID_ARG, "bad AdaGrad chain piece arguments");
+    if (!p->desc.ada_grad || p->desc.value_type != DML_ELEMENT_TYPE_FLOAT)
+        return set_err(DML_E_UNSUPPORTED,
+                       "AdaGrad chained pieces: a handle begun with the AdaGrad descriptor (plain fp32 / fp64: "
+                       "dml_prereduce_chain_piece; int32: dml_group_push_exchange)");
+    if (p->ctx) return set_err(DML_E_UNSUPPORTED, "chained pieces need dml_prereduce_begin (no speculative context)");
+    const AdaPiece ap{base_delta, base_marks, out_delta, out_marks, maxdelta_record, last_piece != 0};
+    return prereduce_piece(p, kChain, row_block, row_stride, row_off, ntask_rows, base_data, out_data, stream, &ap);
 }
 
 int dml_prereduce_timing(int32_t every) {
@@ -2382,6 +2502,7 @@ int dml_prereduce_end(dml_prereduce* p) {
     const bool clean = rc == DML_OK && !p->slots_unread && p->rows_done == p->rows &&
                        reduce_clears_slots(p->desc.value_type, kPreReduce, p->cols);
     if (e == hipSuccess) ws_release(p->device, WsLease{p->ws, p->ws_bytes, clean, p->hctrl, p->rows});
+    if (e == hipSuccess) cand_release(p->device, p->cands);
     prereduce_free(p);
     return rc;
 }

@@ -28,7 +28,8 @@ int32 pushes exactly, intermediates included.
 The order-exact chained reduce-scatter (dml_group_push_chained) is
 bound by NativeShardGroup.push_chained only — the native group is the one the JNI
 deploys; this torch ShardGroup has no chained path. HipOps.chain_piece and
-HipOps.assign expose its two building blocks.
+HipOps.assign expose its two building blocks, HipOps.chain_piece_ada and
+HipOps.assign_ada those of AdaGrad matrices.
 
 Buffer contract of the asynchronous paths (push_full_range, push_exchange,
 push_local): the push buffers must stay allocated and unmodified until flush()
@@ -43,6 +44,9 @@ from typing import List, Optional, Sequence
 from . import _lib
 from .datadesc import DataDesc, KeyRange
 from .store import DataStore, check
+
+
+MAXDELTA_RECORD_BYTES = 32  # DML_MAXDELTA_RECORD_BYTES: [f32 value][i32 row][i32 col][pad][pending candidate]
 
 
 class HipOps:
@@ -84,6 +88,25 @@ class HipOps:
     def assign(self, store: DataStore, src_ptr: int, elems: int) -> None:
         """shard = src (dml_store_assign_dense_device): the owner's commit of a chained slice."""
         check(_lib.load().dml_store_assign_dense_device(store._h, C.c_void_p(src_ptr), elems), store)
+
+    def chain_piece_ada(self, h, block: int, stride: int, off: int, ntask_rows: int, base_data: int, base_delta: int,
+                        base_marks: int, out_data: int, out_delta: int, out_marks: int, record: int, last: bool,
+                        stream: int) -> None:
+        """One chained reduce-scatter step of an AdaGrad matrix (dml_prereduce_chain_piece_ada):
+        data += g and delta += g*g in push order on both planes, touched marks (one uint32 per
+        task row; base_marks 0 = all clear), the maxDelta candidates merged into the device
+        record (MAXDELTA_RECORD_BYTES) and, with `last`, applied to it. out == base works."""
+        check(_lib.load().dml_prereduce_chain_piece_ada(
+            C.c_void_p(h), block, stride, off, ntask_rows, C.c_void_p(base_data), C.c_void_p(base_delta),
+            C.c_void_p(base_marks or None), C.c_void_p(out_data), C.c_void_p(out_delta), C.c_void_p(out_marks),
+            C.c_void_p(record), 1 if last else 0, C.c_void_p(stream)))
+
+    def assign_ada(self, store: DataStore, data_ptr: int, delta_ptr: int, marks_ptr: int, record_ptr: int) -> None:
+        """The owner's commit of a chained AdaGrad slice (dml_store_assign_adagrad_device): data
+        and delta assigned, alpha recomputed where the row is marked and delta > 1, the store's
+        maxDelta = the record's."""
+        check(_lib.load().dml_store_assign_adagrad_device(store._h, C.c_void_p(data_ptr), C.c_void_p(delta_ptr),
+                                                          C.c_void_p(marks_ptr), C.c_void_p(record_ptr)), store)
 
     def end(self, h) -> None:
         check(_lib.load().dml_prereduce_end(C.c_void_p(h)))
@@ -708,8 +731,12 @@ class NativeShardGroup:
 
     def push_chained(self, dev_ptrs: Sequence[int], lens: Sequence[int]) -> None:
         """The order-exact chained reduce-scatter (dml_group_push_chained), fp32 / fp64 plain
-        matrices: shard s ends byte-equal to a reference store fed rank s's pushes, then
-        rank s+1's, ..., rank s-1's. Ranks may pass different numbers of pushes."""
+        matrices and AdaGrad matrices: shard s ends byte-equal to a reference store fed rank
+        s's pushes, then rank s+1's, ..., rank s-1's. Ranks may pass different numbers of
+        pushes. AdaGrad: data, delta, alpha and maxDelta (ties included) are the reference's,
+        with one documented divergence — an element whose delta comes home NaN keeps the alpha
+        the owner held before the call (push_exchange is the path without it).
+        int32 is refused (push_exchange)."""
         n = len(dev_ptrs)
         ptrs = (C.c_void_p * max(n, 1))(*dev_ptrs)
         ls = (C.c_int64 * max(n, 1))(*lens)

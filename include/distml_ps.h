@@ -287,6 +287,27 @@ int dml_store_apply_dense_device(dml_store* s, const void* dev_src, int64_t elem
  * rule is unchanged. dev_src is read on the store's stream: keep it until that
  * stream has passed the copy (an event, or dml_store_flush). */
 int dml_store_assign_dense_device(dml_store* s, const void* dev_src, int64_t elems);
+/* The owner's commit of a chained AdaGrad slice (dml_group_push_chained on an
+ * AdaGrad group), on the store's stream, ordered after every accepted push and
+ * before every later one like dml_store_assign_dense_device. dev_data and
+ * dev_delta hold rows*cols f32 each, dev_marks one uint32 per row (non-zero: some
+ * rank's accepted push listed the row in this call), dev_maxdelta_record the
+ * slice's travelling record (DML_MAXDELTA_RECORD_BYTES). shard data = dev_data,
+ * shard delta = dev_delta; where the row's mark is set and delta > 1,
+ * alpha = (float)(initialAlpha / (factor * sqrt((double)delta))), clamped to
+ * minAlpha, with the store's own parameters (dml_store_set_alpha): inside one
+ * call delta never falls, so that is the alpha the reference's last update of the
+ * element leaves (FloatMatrixStoreAdaGrad.java:268-272). A row no push listed
+ * keeps its alpha even where its delta is above 1 (setAlpha rewrites every
+ * alpha). The store's running maxDelta (value, row, col) becomes the record's.
+ * One divergence: an element whose delta is NaN (a NaN gradient reached it in
+ * this call) keeps the alpha the store held, where the reference leaves the
+ * alpha of its last non-NaN delta above 1; dml_group_push_exchange is the path
+ * without it. The buffers are read on the store's stream: keep them until that
+ * stream has passed the commit. */
+#define DML_MAXDELTA_RECORD_BYTES 32
+int dml_store_assign_adagrad_device(dml_store* s, const void* dev_data, const void* dev_delta, const void* dev_marks,
+                                    const void* dev_maxdelta_record);
 /* Two-moment AdaGrad owner apply: dev_src holds rows x [cols Σu |
  * cols Σu²] f32 (the reduce-scattered dml_prereduce_moments_piece output of the
  * shard's rows); data += Σu, delta += Σu², alpha = initialAlpha / (factor *
@@ -342,11 +363,41 @@ int dml_prereduce_end(dml_prereduce* p);
  * key outside the matrix or a row listed twice in one push, copies dev_base to
  * dev_out (_end reports the error); ascending full-range pushes of a narrow-row
  * matrix are checked key by key before the first piece. DML_E_UNSUPPORTED for
- * int32 and AdaGrad descriptors (use dml_group_push_exchange) and for a handle
+ * int32 and AdaGrad descriptors (AdaGrad: dml_prereduce_chain_piece_ada; int32:
+ * dml_group_push_exchange) and for a handle
  * begun in a speculative context (dml_prereduce_begin_ctx), whose verdict comes
  * after the piece has run. */
 int dml_prereduce_chain_piece(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
                               int64_t ntask_rows, const void* dev_base, void* dev_out, void* stream);
+/* _chain_piece for an AdaGrad matrix (a handle begun with the AdaGrad
+ * descriptor, FloatMatrixStoreAdaGrad): the slice travels as two f32 planes,
+ * data and delta, plus one uint32 touched mark per task row, and a travelling
+ * maxDelta record of DML_MAXDELTA_RECORD_BYTES in device memory (at ring step 0:
+ * the owner's running value, row, col, the rest zero). Row map, stream rule,
+ * completion event and timing are _chain_piece's. Task row t starts from
+ * base_data + t*cols and base_delta + t*cols; every push's record of its model
+ * row is applied in push order as the reference applies it
+ * (FloatMatrixStoreAdaGrad.java:249-284): data += g, delta += g*g, one IEEE
+ * rounding each; both planes are written to out_data / out_delta (out == base
+ * is allowed, plane by plane). All pushes of the handle go through one pass:
+ * the planes are read once and written once whatever the push count. No alpha
+ * is read or written here; the owner computes it once at its commit
+ * (dml_store_assign_adagrad_device). A listed row of a good handle sets
+ * out_marks[t]; other rows copy base_marks[t] (base_marks == NULL reads as all
+ * clear). A row no push lists, a padding row, and every row of a handle whose
+ * index failed are copied bit for bit in both planes. maxDelta: every element's
+ * last strict rise of delta is a candidate; the candidates of this rank's pieces
+ * over one slice merge (largest value, then earliest position in push, record,
+ * column order) and, with last_piece != 0, are applied to the record with the
+ * reference's strict > (FloatMatrixStoreAdaGrad.java:273-277), so an earlier rank
+ * of the ring keeps a tie. Pass last_piece on the last piece of the rank's step
+ * over the slice, and issue one slice's pieces of a handle on one stream.
+ * DML_E_UNSUPPORTED for a plain-fp32 or int32 handle and for a speculative
+ * context's handle. */
+int dml_prereduce_chain_piece_ada(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
+                                  int64_t ntask_rows, const void* base_data, const void* base_delta,
+                                  const void* base_marks, void* out_data, void* out_delta, void* out_marks,
+                                  void* maxdelta_record, int32_t last_piece, void* stream);
 /* The two-moment piece of an AdaGrad matrix's pre-reduce (begun with its desc):
  * task row t's Σu and Σu·u over the pushes, in push order, written as
  * dev_out + t*2*cols = [cols Σu | cols Σu²] (f32; rows of whole 16-B vectors
@@ -464,7 +515,8 @@ int dml_group_push_moments(dml_group* g, const void* const* dev_bufs, const int6
  * every earlier group call's apply; no collective. */
 int dml_group_push_local(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n);
 /* Order-exact chained reduce-scatter of the rank's n (0 <= n <= 64; ranks may
- * differ) full-range pushes, for plain fp32 / fp64 matrices. Owner s's slice
+ * differ) full-range pushes, for fp32 / fp64 matrices, plain or AdaGrad (below).
+ * Owner s's slice
  * starts as shard s and walks the ring s, s+1, ..., s-1: every rank adds its own
  * pushes' rows of the slice in push order, one IEEE rounding per add
  * (dml_prereduce_chain_piece), and forwards it with ncclSend / ncclRecv; the last
@@ -491,9 +543,24 @@ int dml_group_push_local(dml_group* g, const void* const* dev_bufs, const int64_
  * pieces, is returned by this call; a key outside the matrix or a row listed
  * twice in one push (found by the key index on the device) is returned by the
  * rank's next group call or by dml_group_flush.
- * At world 1 the call is dml_store_push_batch_device. int32 and AdaGrad
- * descriptors: DML_E_UNSUPPORTED (use dml_group_push_exchange), on every rank
- * alike and before any send. */
+ * AdaGrad groups (FloatMatrixStoreAdaGrad): the slice carries data, delta, one
+ * touched mark per row and the maxDelta record, each sub-chunk one message
+ * (dml_prereduce_chain_piece_ada); about two planes' bytes per rank over xGMI.
+ * After the call shard s holds the state of one FloatMatrixStoreAdaGrad over its
+ * key range fed the same ring order (FloatMatrixStoreAdaGrad.java:239-284): data
+ * and delta bit for bit; alpha bit for bit, computed once at the owner's commit
+ * (dml_store_assign_adagrad_device) with the owner's parameters, on rows some
+ * rank's accepted push listed in this call; maxDelta value, row and col, ties
+ * included (the first in ring rank, push, record, column order holds it). A
+ * failed rank marks no row and changes no maxDelta record. One documented
+ * divergence, and no other: an element whose delta comes home NaN (a NaN
+ * gradient reached it in this call) keeps the alpha the owner's store held
+ * before the call, where the reference leaves the alpha of its last non-NaN
+ * delta above 1; its data and delta are exact. dml_group_push_exchange is the
+ * path without this divergence.
+ * At world 1 the call is dml_store_push_batch_device. int32 descriptors:
+ * DML_E_UNSUPPORTED (use dml_group_push_exchange), on every rank alike and
+ * before any send. */
 int dml_group_push_chained(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n);
 int dml_group_flush(dml_group* g);
 void dml_group_destroy(dml_group* g);

@@ -45,13 +45,16 @@ public class GpuShardGroup implements AutoCloseable {
     public void pushLocal(long[] devPtrs, long[] lens) { nativeGroupPush(handle, devPtrs, lens, 3); }
 
     /**
-     * Order-exact path for plain float / double matrices: each shard's slice walks the ring
+     * Order-exact path for float / double matrices, plain or AdaGrad: each shard's slice walks the ring
      * of ranks and every rank adds its own pushes' rows in push order, so shard s ends
      * byte-equal to a FloatMatrixStore / DoubleMatrixStore fed rank s's pushes, then rank
      * s+1's, ... (an arrival order PSAgent's selector may produce, PSAgent.java:166-186).
      * One model's bytes per rank over xGMI, whatever the number of pushes; ranks may pass
-     * different numbers (0..64). int / AdaGrad formats throw a RuntimeException that names
-     * pushExchange's native call.
+     * different numbers (0..64). An AdaGrad matrix (FloatMatrixStoreAdaGrad) ends with that
+     * store's data, delta, alpha and maxDelta / maxDeltaRow / maxDeltaCol, byte for byte, with
+     * one documented divergence: an element whose delta comes home NaN keeps the alpha its
+     * owner held before the call (pushExchange is the path without it). int formats throw a
+     * RuntimeException that names pushExchange's native call.
      */
     public void pushChained(long[] devPtrs, long[] lens) { nativeGroupPush(handle, devPtrs, lens, 4); }
 

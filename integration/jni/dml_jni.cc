@@ -327,7 +327,7 @@ JNIEXPORT jlong JNICALL GFN(nativeGroupCreate)(JNIEnv* env, jclass, jbyteArray i
 }
 
 // mode: 0 full-range pre-reduce, 1 exact exchange, 2 two-moment AdaGrad, 3 local (already split),
-// 4 order-exact chained reduce-scatter (fp32 / fp64)
+// 4 order-exact chained reduce-scatter (fp32 / fp64, plain or AdaGrad)
 JNIEXPORT void JNICALL GFN(nativeGroupPush)(JNIEnv* env, jclass, jlong g, jlongArray ptrs, jlongArray lens,
                                              jint mode) {
     const jsize n = env->GetArrayLength(ptrs);
