@@ -79,6 +79,7 @@ SIGNATURES = {
     "dml_store_apply_dense_device": (C.c_int, [_vp, _vp, _i64]),
     "dml_store_assign_dense_device": (C.c_int, [_vp, _vp, _i64]),
     "dml_store_assign_adagrad_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "dml_store_assign_dense_i32_device": (C.c_int, [_vp, _vp, _i64, _vp]),
     "dml_store_apply_adagrad_moments_device": (C.c_int, [_vp, _vp, _i64]),
     "dml_reduce_buckets_dense": (C.c_int, [_P(dml_desc), _i64, _i64, _i32, _P(_vp), _P(_i64), _i32, _vp, _vp]),
     "dml_prereduce_begin": (C.c_int, [_P(dml_desc), _i64, _i64, _i32, _P(_vp), _P(_i64), _i32, _vp, _P(_vp)]),
@@ -86,6 +87,8 @@ SIGNATURES = {
     "dml_prereduce_chain_piece": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "dml_prereduce_chain_piece_ada": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
                                                 _vp]),
+    "dml_prereduce_chain_piece_i32": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "dml_prereduce_chain_close_i32": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _vp]),
     "dml_prereduce_end": (C.c_int, [_vp]),
     "dml_prereduce_moments_piece": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "dml_prereduce_stream_wait": (C.c_int, [_vp, _vp]),
@@ -106,6 +109,7 @@ SIGNATURES = {
     "dml_group_push_full_range": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
     "dml_group_push_local": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
     "dml_group_push_chained": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
+    "dml_group_push_chained_i32": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
     "dml_group_debug_fail_verify": (C.c_int, [_vp, _i32]),
     "dml_group_flush": (C.c_int, [_vp]),
     "dml_group_destroy": (None, [_vp]),

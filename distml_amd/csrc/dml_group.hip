@@ -27,6 +27,9 @@
 // the maxDelta record; the owner computes alpha once at its commit. One documented
 // divergence there (the alpha of an element whose delta comes home NaN, DESIGN.md
 // §2); dml_group_push_exchange is the path without it.
+// dml_group_push_chained_i32 is the same ring for dense int32 matrices (IntMatrixStore):
+// every slice carries a 32-byte verdict record, every add is checked, and no sub-chunk
+// leaves a rank before the rank's whole step over the slice has its verdict.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -123,6 +126,9 @@ struct dml_group {
     hipEvent_t cready = nullptr;     // store stream: every earlier call's apply is enqueued before it
     std::deque<dml_prereduce*> cpending;  // calls whose index errors are not yet collected
     int ck = 0;
+    // int32 chain: a commit's verdict record is on its way to the host; a non-chained
+    // call behind it waits for it first (the reference refuses pushes to a closed store)
+    bool cverdict = false;
 };
 
 namespace {
@@ -220,6 +226,13 @@ int end_handles(std::deque<dml_prereduce*>& q, size_t keep) {
 }
 int end_moments(dml_group* g, size_t keep) { return end_handles(g->mpending, keep); }
 int end_chained(dml_group* g, size_t keep) { return end_handles(g->cpending, keep); }
+// The last int32 chained commit's verdict, waited for: a closed record puts the store into
+// its error state (DML_E_NEGATIVE_COUNTER) before the caller hands it anything else.
+int chain_i32_verdict(dml_group* g) {
+    if (!g->cverdict) return DML_OK;
+    g->cverdict = false;
+    return store_chain_i32_collect(g->store, true);
+}
 
 void group_free(dml_group* g) {
     if (!g) return;
@@ -414,6 +427,7 @@ int dml_group_push_full_range(dml_group* g, const void* const* dev_bufs, const i
         GRC(hand_over(g));
     }
     GRC(end_chained(g, 0));  // chained calls are committed on the store's stream already: their index errors
+    GRC(chain_i32_verdict(g));
     GRC(ensure_partials(g));
     const int64_t S = g->step_rows, P = g->pieces;
     if (S % P) return set_error(DML_E_INVALID_ARG, "pieces must divide the linearSplit step");
@@ -453,7 +467,12 @@ int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int
     // applies calls in order
     GRC(end_pending(g, 0));
     GRC(end_chained(g, 0));
+    // an int32 chained call's verdict: the store is in its error state before this call's
+    // slices reach it (they are refused at their hand-over). Returned after the
+    // exchanges: the rank never leaves them.
+    const int verdict = chain_i32_verdict(g);
     const int W = g->world;
+    if (W == 1 && verdict != DML_OK) return verdict;
     const int64_t K = g->desc.key_type == 0 ? 4 : 8;
     const int64_t stride = g->desc.data_type == DML_DATA_TYPE_MATRIX ? K + (int64_t)g->vbytes * g->cols
                                                                       : K + (int64_t)g->vbytes;
@@ -552,7 +571,7 @@ int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int
         }
     g->xheld = true;
     g->xheld_set = i;
-    return local;
+    return local != DML_OK ? local : verdict;
 }
 
 int dml_group_push_moments(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
@@ -627,6 +646,7 @@ int dml_group_push_local(dml_group* g, const void* const* dev_bufs, const int64_
     }
     GRC(end_pending(g, 0));  // full-range calls waiting for their reduce-scatter and apply
     GRC(end_chained(g, 0));  // chained calls' commits are on the store's stream already: their index errors
+    GRC(chain_i32_verdict(g));
     return dml_store_push_batch_device(g->store, dev_bufs, lens, n);
 }
 
@@ -832,6 +852,155 @@ int dml_group_push_chained(dml_group* g, const void* const* dev_bufs, const int6
     return prior != DML_OK ? prior : first != DML_OK ? first : commit != DML_OK ? commit : older;
 }
 
+// The chained reduce-scatter of a dense int32 matrix (contract: include/distml_ps.h).
+// The ring, buffers, events and failed-rank rule are dml_group_push_chained's. A slice
+// buffer holds [record 32 B][rows]: sub-chunk 0's message starts at the record, so the
+// verdict is on the rank before any piece of the step runs. Step t on rank r, slice
+// q = (r - t) mod N, all on cstream: P pieces (dml_prereduce_chain_piece_i32, each
+// waiting for its own sub-chunk's receive), then one close over the whole slice
+// (dml_prereduce_chain_close_i32: rollback past the step's first negative, verdict);
+// only then do the step's P send / receive groups follow on rstream. The first-negative
+// word of a step is the handle's Ctrl::neg_pos (all ones after dml_prereduce_begin,
+// handed back so by every close).
+int dml_group_push_chained_i32(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
+    if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
+        return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
+    // the same answer on every rank, before any send: nobody waits for a peer
+    if (!g->plain || !g->desc.dense_column || g->desc.value_type != DML_ELEMENT_TYPE_INT)
+        return set_error(DML_E_UNSUPPORTED,
+                         "dml_group_push_chained_i32 serves dense int32 matrices (fp32 / fp64, plain or AdaGrad: "
+                         "dml_group_push_chained)");
+    GHIP(hipSetDevice(g->device));
+    int held = DML_OK;  // an exchange call's slices come first; a refusal there does not keep the rank off the ring
+    if (g->xheld) {
+        GHIP(hipStreamSynchronize(g->rstream));
+        held = hand_over(g);
+    }
+    const int W = g->world, P = g->pieces;
+    if (W == 1) {  // one owner: the store's own ordered, checked push is the chain
+        GRC(held);
+        GRC(end_pending(g, 0));
+        return dml_store_push_batch_device(g->store, dev_bufs, lens, n);
+    }
+    int prior = end_pending(g, 0);
+    if (prior == DML_OK) prior = held;
+    const int64_t C = g->cols;
+    const size_t rowb = (size_t)C * g->vbytes;
+    constexpr size_t kRec = sizeof(ChainI32Rec);
+    std::vector<int64_t> f((size_t)W), l((size_t)W);
+    GRC(dml_linear_split(0, g->total_rows - 1, W, f.data(), l.data()));
+    if (!g->cbuf[0][0]) {  // first chained call: a group that never makes one pays nothing
+        for (int i = 0; i < 2; ++i) {
+            for (int j = 0; j < 2; ++j) GHIP(hipMalloc(&g->cbuf[i][j], kRec + (size_t)g->step_rows * rowb));
+            g->cev[i].resize((size_t)2 * W * P, nullptr);
+            for (hipEvent_t& e : g->cev[i]) GHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        GHIP(hipEventCreateWithFlags(&g->cready, hipEventDisableTiming));
+    }
+    const int set = g->ck;
+    g->ck ^= 1;
+    int first = DML_OK;  // the rank's first local failure of this call
+    auto note = [&](int rc) {
+        if (rc != DML_OK && first == DML_OK) first = rc;
+    };
+    auto hip = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess) note(set_error(DML_E_HIP, std::string(what) + ": " + hipGetErrorString(e)));
+    };
+    dml_prereduce* h = nullptr;
+    note(dml_prereduce_begin(&g->desc, 0, g->total_rows, g->cols, dev_bufs, lens, n, g->istream, &h));
+    // The shard as every earlier call leaves it. A store the host knows to be closed (its
+    // error state: a negative counter of an earlier push, or a verdict already collected;
+    // one that has just come home is looked at without waiting) is no failure of this
+    // call: the rank's pushes still go to the other shards; its own slice travels closed.
+    uint64_t seq = 0;
+    void* shard = nullptr;
+    void* srec = nullptr;
+    int closed = DML_OK;
+    int rs = dml_store_push_seq(g->store, &seq);
+    if (rs == DML_OK) rs = dml_store_retire(g->store, seq);
+    if (rs == DML_OK) closed = store_chain_i32_collect(g->store, false);
+    if (rs == DML_E_NEGATIVE_COUNTER) {
+        closed = rs;
+        rs = DML_OK;
+    }
+    if (closed != DML_OK && closed != DML_E_NEGATIVE_COUNTER) {  // any other store failure: the call's own
+        rs = closed;
+        closed = DML_OK;
+    }
+    note(rs);
+    GRC(dml_store_device_ptr(g->store, &shard));
+    GRC(store_chain_i32_record(g->store, &srec));
+    hip(hipEventRecord(g->cready, g->sstream), "hipEventRecord");
+    hip(hipStreamWaitEvent(g->cstream, g->cready, 0), "hipStreamWaitEvent");
+    uint8_t* const B[2] = {(uint8_t*)g->cbuf[set][0], (uint8_t*)g->cbuf[set][1]};
+    hipEvent_t* const pdone = g->cev[set].data();
+    hipEvent_t* const rdone = pdone + (size_t)W * P;
+    const int nxt = (g->rank + 1) % W, prv = (g->rank + W - 1) % W;
+    int crc = DML_OK;  // the transfers' own status
+    auto sub = [&](int q, int k, int64_t* r0, int64_t* nr) {
+        const int64_t rows = l[(size_t)q] - f[(size_t)q] + 1, per = (rows + P - 1) / P;
+        *r0 = std::min<int64_t>((int64_t)k * per, rows);
+        *nr = std::min<int64_t>(per, rows - *r0);
+    };
+    // step 0's record: the store's device-resident one (a shard an earlier call closed takes
+    // no add although the host has not seen that verdict yet), or closed outright
+    if (closed != DML_OK) hip(hipMemsetAsync(B[0], 0, kRec, g->cstream), "hipMemsetAsync");
+    else hip(hipMemcpyAsync(B[0], srec, kRec, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+    for (int t = 0; t < W; ++t) {
+        const int q = (g->rank - t + W) % W, qin = (q + W - 1) % W;
+        uint8_t* const cur = B[t & 1];       // step t's slice (t > 0: arrived here in step t - 1)
+        uint8_t* const in = B[(t + 1) & 1];  // slice qin lands here
+        const int64_t qrows = l[(size_t)q] - f[(size_t)q] + 1;
+        for (int k = 0; k < P; ++k) {
+            int64_t r0, nr;
+            sub(q, k, &r0, &nr);
+            if (nr <= 0 && k > 0) continue;
+            uint8_t* const out = cur + kRec + (size_t)r0 * rowb;
+            const uint8_t* const base = t == 0 ? (const uint8_t*)shard + (size_t)r0 * rowb : out;
+            if (t > 0) hip(hipStreamWaitEvent(g->cstream, rdone[(t - 1) * P + k], 0), "hipStreamWaitEvent");
+            if (nr <= 0) continue;
+            if (first == DML_OK) note(dml_prereduce_chain_piece_i32(h, nr, nr, f[(size_t)q] + r0, nr, base, out, cur, g->cstream));
+            // a failed rank forwards the slice as it holds it (step 0: its own shard's rows, the seeded record)
+            if (first != DML_OK && t == 0)
+                hip(hipMemcpyAsync(out, base, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+        }
+        // the slice's verdict, before any of it leaves the rank
+        if (first == DML_OK)
+            note(dml_prereduce_chain_close_i32(h, qrows, qrows, f[(size_t)q], qrows, cur + kRec, cur, t, g->cstream));
+        hip(hipEventRecord(pdone[t], g->cstream), "hipEventRecord");
+        hip(hipStreamWaitEvent(g->rstream, pdone[t], 0), "hipStreamWaitEvent");
+        for (int k = 0; k < P; ++k) {
+            int64_t r0, nr, i0, ni;
+            sub(q, k, &r0, &nr);
+            sub(qin, k, &i0, &ni);
+            // sub-chunk 0's message starts at the record; every rank issues every group (empty ones: zero bytes)
+            const uint8_t* const src = k == 0 ? cur : cur + kRec + (size_t)r0 * rowb;
+            uint8_t* const land = k == 0 ? in : in + kRec + (size_t)i0 * rowb;
+            const size_t sbytes = (size_t)nr * rowb + (k == 0 ? kRec : 0), rbytes = (size_t)ni * rowb + (k == 0 ? kRec : 0);
+            ncclResult_t r = ncclGroupStart();
+            if (r == ncclSuccess) r = ncclSend(src, sbytes, ncclUint8, nxt, g->comm, g->rstream);
+            if (r == ncclSuccess) r = ncclRecv(land, rbytes, ncclUint8, prv, g->comm, g->rstream);
+            const ncclResult_t re = ncclGroupEnd();
+            if (r == ncclSuccess) r = re;
+            if (r != ncclSuccess && crc == DML_OK)
+                crc = set_error(DML_E_HIP, std::string("chained ncclSend/ncclRecv: ") + ncclGetErrorString(r));
+            hip(hipEventRecord(rdone[t * P + k], g->rstream), "hipEventRecord");
+        }
+    }
+    // home: step N-1 received the rank's own slice and its record. A store known closed
+    // commits nothing (the slice came home as it left).
+    hip(hipStreamWaitEvent(g->sstream, rdone[(W - 1) * P + P - 1], 0), "hipStreamWaitEvent");
+    int commit = crc;
+    if (commit == DML_OK && closed == DML_OK) {
+        commit = dml_store_assign_dense_i32_device(g->store, B[W & 1] + kRec, g->shard_rows * C, B[W & 1]);
+        if (commit == DML_OK) g->cverdict = true;
+    }
+    if (h) g->cpending.push_back(h);
+    const int older = end_chained(g, 1);  // the previous chained call's key / repeated-row errors
+    return prior != DML_OK ? prior : first != DML_OK ? first : commit != DML_OK ? commit : older != DML_OK ? older : closed;
+}
+
 int dml_group_debug_fail_verify(dml_group* g, int32_t nth) {
     if (!g || nth < 0) return set_error(DML_E_INVALID_ARG, "bad fault-injection arguments");
     g->fail_verify_at = nth;
@@ -852,6 +1021,8 @@ int dml_group_flush(dml_group* g) {
     if (rc == DML_OK) rc = rm;
     const int rch = end_chained(g, 0);
     if (rc == DML_OK) rc = rch;
+    const int rcv = chain_i32_verdict(g);
+    if (rc == DML_OK) rc = rcv;
     for (hipStream_t s : {g->cstream, g->rstream})
         if (hipStreamSynchronize(s) != hipSuccess && rc == DML_OK) rc = set_error(DML_E_HIP, "group stream sync");
     for (hipEvent_t e : g->applied)

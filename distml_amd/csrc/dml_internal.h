@@ -140,6 +140,8 @@ struct RowMap {
     int64_t rows_total = 0;
     void* out = nullptr;
     const void* base = nullptr;
+    // kChainCheckI32: the slice's travelling verdict record (ChainI32Rec); closed = copy
+    const void* rec = nullptr;
     // model row of task row t (rows <= INT32_MAX, a Java array: 32-bit division)
     __host__ __device__ inline int64_t row(int64_t t) const {
         if (!block) return t;
@@ -167,7 +169,24 @@ enum ReduceMode : int {
     // would turn -0.0 into +0.0). A handle whose index met a key outside the matrix
     // or a repeated row adds nothing: every row is copied.
     kChain = 5,
+    // Chained reduce-scatter step of an int32 matrix: kChain's row rules with
+    // kAddCheckI32's check after every add. The first position (push << 40 | byte
+    // offset) that left a counter negative goes to Ctrl::neg_pos by atomicMin; every
+    // add is made (kRollbackI32 through the piece's row map undoes the later ones once
+    // the whole slice has been summed). A slice whose record (RowMap::rec) arrived
+    // closed is copied bit for bit, like one whose handle's index failed.
+    kChainCheckI32 = 6,
 };
+// The verdict record an int32 slice carries round the ring, at the head of its first
+// sub-chunk's message (DML_CHAIN_I32_RECORD_BYTES; 8-byte aligned). Open: pos == kNoPos.
+struct ChainI32Rec {
+    unsigned long long pos;  // (push << 40) | byte offset of the failing add in the closing rank's push
+    long long key;           // IllegalStateException(key, col), IntMatrixStore.java:174-176
+    int32_t col;
+    int32_t step;            // ring step at which the slice closed
+    unsigned long long pad;
+};
+static_assert(sizeof(ChainI32Rec) == 32, "ChainI32Rec layout (DML_CHAIN_I32_RECORD_BYTES)");
 // kChain: the index's verdict, read by every wave (nothing of a failed call is added)
 __host__ __device__ inline bool ctrl_index_failed(const Ctrl* c) {
     const unsigned long long cut = c->cutoff;
@@ -206,7 +225,13 @@ hipError_t launch_reduce(int vtype, int mode, void* shard, int64_t rows, int32_t
                          LaunchEv ev = {}, RowMap rm = {});
 hipError_t launch_rollback_i32(int32_t* shard, int64_t rows, int32_t cols, const Batch& bt, int nb,
                                int64_t stride, int K, const int32_t* slot, const uint32_t* rowflag, Ctrl* ctrl,
-                               uint64_t tail_cut, hipStream_t st);
+                               uint64_t tail_cut, hipStream_t st, RowMap rm = {});
+// After the chained int32 step's rollback (one wave): a set Ctrl::neg_pos closes an open
+// record (pos, the key read from the push at pos, col, ring step); the word is reset.
+hipError_t launch_chain_i32_verdict(const Batch& bt, int nb, int64_t stride, int K, Ctrl* ctrl, ChainI32Rec* rec,
+                                    int32_t step, hipStream_t st, LaunchEv ev = {});
+// The owner's commit: the home record closes the store's open record (sticky).
+hipError_t launch_chain_i32_merge(ChainI32Rec* store_rec, const ChainI32Rec* home, hipStream_t st);
 // `cand` holds n candidates plus kMdParts entries of scratch after them.
 constexpr int kMdParts = 256;
 hipError_t launch_maxdelta_finalize(DeltaCand* cand, int64_t n, MaxDelta* md, const Batch& bt, int nb,
@@ -408,5 +433,11 @@ int set_error(int code, const std::string& msg);
 int store_assign_adagrad(dml_store* s, int64_t row0, int64_t nrows, const void* data, const void* delta,
                          const void* marks, const void* rec);
 int store_adagrad_ptrs(dml_store* s, float** delta, void** maxdelta);
+// The int32 store's side of a chained call, for the group: the device address of its
+// sticky closed record (allocated open on first use), and the verdict of the commits
+// enqueued so far (`block`: wait for the last one) — a closed record puts the store into
+// its error state, DML_E_NEGATIVE_COUNTER with the record's key and col.
+int store_chain_i32_record(dml_store* s, void** dev_rec);
+int store_chain_i32_collect(dml_store* s, bool block);
 
 }  // namespace dml

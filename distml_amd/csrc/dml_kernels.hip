@@ -18,6 +18,10 @@
 //                   (data + delta planes, touched marks, maxDelta candidates; one
 //                   documented divergence, the alpha of an element whose delta comes
 //                   home NaN — dml_group_push_exchange is the path without it)
+//   k_chain_i32_verdict, k_chain_i32_merge  the chained reduce-scatter of int32
+//                   matrices: kChainCheckI32 (k_reduce_rows / k_reduce) sums a step
+//                   with the check after every add, k_reduce<kRollbackI32> undoes the
+//                   adds past the first negative, the verdict closes the slice's record
 //   k_fetch, k_bswap, k_fill, k_apply_dense, k_synth_*  — fetch / checkpoint /
 //                   init / owner-apply / synthetic data.
 #include "dml_device.h"
@@ -283,33 +287,47 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
     static_assert(CPW == 1 || CPW == 2 || CPW == 4, "1, 2 or 4 chunks per wave");
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t task = (int64_t)blockIdx.x * WPB + wid;
+    int64_t task = (int64_t)blockIdx.x * WPB + wid;
     const int64_t ntask = rows * (int64_t)ngroups;
+    // kRollbackI32 runs a capped grid (launch_reduce_t) whose waves stride over the tasks and
+    // leave at once when there is nothing to undo: a chained int32 step launches it every
+    // time, over a whole slice; every other mode runs one task per wave
+    if constexpr (MODE == kRollbackI32)
+        if (ctrl->neg_pos == kNoPos) return;
+    // the chained steps (kChain, kChainCheckI32): rows start from RowMap::base, every row is written
+    constexpr bool kChainLike = MODE == kChain || MODE == kChainCheckI32;
+    constexpr bool kCheck = MODE == kAddCheckI32 || MODE == kChainCheckI32;
 
     // AdaGrad maxDelta candidate of this lane.
     float cand_v = 0.f;
     uint64_t cand_p = kNoPos;
     bool cand_ok = false;
 
-    if (task < ntask) do {
+    for (;;) {
+    if (task >= ntask) break;
+    do {
         if (bt.prev && ctrl_abnormal(bt.prev)) break;  // predecessor needs the host first
         const int64_t trow = task / ngroups;
         const int cg = (int)(task - trow * ngroups);
         const int64_t row = rm.row(trow);
         T* const rowp = rm.out ? (T*)rm.out + trow * (int64_t)cols : shard + row * (int64_t)cols;
         // kChain: the row as it arrived (may be rowp itself: this lane alone touches its elements)
-        const T* const basep = MODE == kChain ? (const T*)rm.base + trow * (int64_t)cols : nullptr;
+        const T* const basep = kChainLike ? (const T*)rm.base + trow * (int64_t)cols : nullptr;
         if (rm.block && row >= rm.rows_total) {  // padding row of a short last shard
+            if (MODE == kRollbackI32) break;  // (a chained slice's rollback: nothing was added to it)
 #pragma unroll
             for (int c = 0; c < CPW; ++c) {
                 const int32_t cc = ((cg * CPW + c) * 64 + lane) * VEC;
                 for (int e = 0; e < VEC; ++e)
-                    if (cc + e < cols) rowp[cc + e] = MODE == kChain ? basep[cc + e] : T(0);
+                    if (cc + e < cols) rowp[cc + e] = kChainLike ? basep[cc + e] : T(0);
             }
             break;
         }
-        // kChain: a call whose index failed adds nothing (every row is copied)
-        const int nbe = (MODE == kChain && ctrl_index_failed(ctrl)) ? 0 : nb;
+        // kChain: a call whose index failed adds nothing (every row is copied);
+        // kChainCheckI32: nor does any call to a slice whose record arrived closed
+        bool dead = kChainLike && ctrl_index_failed(ctrl);
+        if constexpr (MODE == kChainCheckI32) dead |= ((const ChainI32Rec*)rm.rec)->pos != kNoPos;
+        const int nbe = dead ? 0 : nb;
         if (rowflag && rowflag[row]) break;  // a push repeats this row: the host replays it exactly
 
         int32_t c0[CPW];
@@ -337,6 +355,11 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
             if (negcut == kNoPos) break;
         }
         const int32_t* srow = slot + row * slot_stride(nb);
+        // a chained int32 step and its rollback: slot = row for the pushes k_ident_full
+        // confirmed (Batch::ident_ok: the index wrote no slots for them)
+        uint64_t rb_ident = 0;
+        if constexpr (MODE == kRollbackI32 || MODE == kChainCheckI32)
+            if (bt.ident_ok) rb_ident = ctrl->ident;
 
         T acc[CPW][VEC];
         // AdaGrad: delta; the delta after the last push that left it above 1 (0 =
@@ -354,7 +377,7 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
                 if (MODE == kPreReduce) {
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) acc[c][e] = T(0);
-                } else if (MODE == kChain) {
+                } else if (kChainLike) {
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) acc[c][e] = e < nv[c] ? basep[c0[c] + e] : T(0);
                 } else if (nv[c] == VEC) {
@@ -388,7 +411,7 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
                 if (p > negcut) acc[c][e] = (T)((uint32_t)acc[c][e] - (uint32_t)u);
             } else {
                 acc[c][e] = Elem<T>::add(acc[c][e], u);
-                if constexpr (MODE == kAddCheckI32) {
+                if constexpr (kCheck) {
                     if (!negf && acc[c][e] < 0) { negf = true; negpos = p; }
                 }
                 if constexpr (MODE == kAdaGrad) {
@@ -425,6 +448,9 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
                     gbv[h + g] = in ? gv[g] : INT_MAX;
                     bp[h + g] = (const uint8_t*)pv[g];
                     rr[h + g] = (in && gbv[h + g] <= cut_b) ? sv[g] : -1;
+                    if constexpr (MODE == kRollbackI32 || MODE == kChainCheckI32)
+                        if (rb_ident && in && ctrl_identity(ctrl, rb_ident, b0 + h + g))
+                            rr[h + g] = row < bt.nrec[b0 + h + g] ? (int32_t)row : -1;
                 }
             }
             bool any = false;
@@ -510,7 +536,7 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
                 for (int e = 0; e < VEC; ++e) acc[c][e] = T(0);
             touched = true;
         }
-        if (MODE == kChain && !touched) {  // no push lists the row: copied as it arrived
+        if (kChainLike && !touched) {  // no push lists the row: copied as it arrived
             load_row();
             touched = true;
         }
@@ -559,8 +585,11 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
                 }
             }
         }
-        if (MODE == kAddCheckI32 && negf) atomicMin(&ctrl->neg_pos, (unsigned long long)negpos);
+        if (kCheck && negf) atomicMin(&ctrl->neg_pos, (unsigned long long)negpos);
     } while (0);
+    if constexpr (MODE != kRollbackI32) break;  // one task per wave
+    task += (int64_t)gridDim.x * WPB;
+    }
 
     if constexpr (MODE == kAdaGrad) {
         cand_block_best<WPB>(cand_ok, cand_v, cand_p);
@@ -601,7 +630,11 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
                                                      const uint32_t* __restrict__ rowflag, Ctrl* __restrict__ ctrl,
                                                      uint64_t tail_cut, RowMap rm) {
     constexpr int VEC = Elem<T>::VEC;
-    static_assert(MODE == kAdd || MODE == kAddCheckI32 || MODE == kPreReduce || MODE == kChain, "plain-sum modes only");
+    static_assert(MODE == kAdd || MODE == kAddCheckI32 || MODE == kPreReduce || MODE == kChain || MODE == kChainCheckI32,
+                  "plain-sum modes only");
+    // the chained steps (kChain, kChainCheckI32): rows start from RowMap::base, every row is written
+    constexpr bool kChainLike = MODE == kChain || MODE == kChainCheckI32;
+    constexpr bool kCheck = MODE == kAddCheckI32 || MODE == kChainCheckI32;
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // DEPTH 3 (rows that are not whole lines, e.g. config 5's 4000-B rows): XCD-
@@ -642,14 +675,14 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
         const int64_t tr = trow < rows ? trow : tb * RPW;
         row[r] = rm.row(tr);
         rowp[r] = rm.out ? (T*)rm.out + tr * (int64_t)cols : shard + row[r] * (int64_t)cols;
-        basep[r] = MODE == kChain ? (const T*)rm.base + tr * (int64_t)cols : nullptr;
+        basep[r] = kChainLike ? (const T*)rm.base + tr * (int64_t)cols : nullptr;
         if (trow >= rows) continue;
         if (rm.block && row[r] >= rm.rows_total) {  // padding row of a short last shard: zeros (kChain: copied)
 #pragma unroll
             for (int c = 0; c < CPW; ++c)
 #pragma unroll
                 for (int e = 0; e < VEC; ++e)
-                    if (e < nv[c]) rowp[r][c0[c] + e] = MODE == kChain ? basep[r][c0[c] + e] : T(0);
+                    if (e < nv[c]) rowp[r][c0[c] + e] = kChainLike ? basep[r][c0[c] + e] : T(0);
             continue;
         }
         // a push repeats this row: the host replays it exactly (a keeping chunk's index
@@ -657,7 +690,7 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
         if (rowflag && !bt.keeps && rowflag[row[r]]) continue;
         // a row no push of the chunk lists: its shard row is neither read nor written
         // (the index marked the listed ones; the load runs beside the flag load above)
-        if (MODE != kPreReduce && MODE != kChain && bt.listed && !bt.listed[row[r]]) continue;
+        if (MODE != kPreReduce && !kChainLike && bt.listed && !bt.listed[row[r]]) continue;
         live |= 1u << r;
         if (!fb) fb = (const uint8_t*)rowp[r];
     }
@@ -683,13 +716,16 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
             ident = ctrl->ident;
         }
     }
-    if constexpr (MODE == kPreReduce || MODE == kChain)
+    if constexpr (MODE == kPreReduce || kChainLike)
         if (bt.ident_ok) ident = ctrl->ident;  // verified before the launch: slot = row, no key checks
 
-    if constexpr (MODE == kChain) {
+    if constexpr (kChainLike) {
         // a call whose index failed (key outside the matrix, repeated row) adds nothing:
-        // the wave's rows are copied as they arrived
-        if (cut != kNoPos || ctrl->no_dup == 0u) {
+        // the wave's rows are copied as they arrived; kChainCheckI32: so is every row of
+        // a slice whose record arrived closed (the shard takes no add from anyone)
+        bool dead = cut != kNoPos || ctrl->no_dup == 0u;
+        if constexpr (MODE == kChainCheckI32) dead |= ((const ChainI32Rec*)rm.rec)->pos != kNoPos;
+        if (dead) {
             for (int r = 0; r < RPW; ++r) {
                 if (!(live >> r & 1u)) continue;
                 for (int c = 0; c < CPW; ++c)
@@ -740,7 +776,7 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
         for (int c = 0; c < CPW; ++c) {
             const bool ld = MODE != kPreReduce && (live >> r & 1u);
             // the input row: in place, or the speculative chunk's input buffer
-            const T* const lrow = MODE == kChain                 ? basep[r]
+            const T* const lrow = kChainLike                     ? basep[r]
                                   : (MODE == kAdd && bt.src) ? (const T*)bt.src + row[r] * (int64_t)cols
                                                              : rowp[r];
             if (ld && nv[c] == VEC) {
@@ -769,7 +805,8 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
         vslot[r] = ((live >> r & 1u) && lane < nb)
                        ? (lane_ident ? (row[r] < bt.nrec[lane] ? (int32_t)row[r] : -1) : slot[row[r] * slot_stride(nb) + lcol])
                        : -1;
-    if (!bt.spec && ngroups == 1) {
+    // (kChainCheckI32 keeps the table: the step's rollback reads it after the pieces)
+    if (MODE != kChainCheckI32 && !bt.spec && ngroups == 1) {
         // Hand the slot rows back as the next batch's index expects them (-1 = no
         // record), so the host skips the slot-table memset (reduce_clears_slots); the
         // int32 rollback (rare) rebuilds the table with a second index. Only when this
@@ -803,7 +840,7 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
         if (aligned) {
 #pragma unroll
             for (int e = 0; e < VEC; ++e) a[e] = Elem<T>::add(a[e], t[e]);
-            if constexpr (MODE == kAddCheckI32)
+            if constexpr (kCheck)
                 negbits |= nv[c] > 0 ? ((uint32_t)a[0] | (uint32_t)a[1] | (uint32_t)a[2] | (uint32_t)a[3]) : 0u;
         } else {
             T u[VEC];
@@ -817,7 +854,7 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
             for (int e = 0; e < VEC; ++e)
                 if (e < nv[c]) {
                     a[e] = Elem<T>::add(a[e], u[e]);
-                    if constexpr (MODE == kAddCheckI32) negbits |= (uint32_t)a[e];
+                    if constexpr (kCheck) negbits |= (uint32_t)a[e];
                 }
         }
     };
@@ -976,9 +1013,10 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
         }
     }
 
-    if constexpr (MODE == kAddCheckI32) {
+    if constexpr (kCheck) {
         // neg_first: some add left a counter negative. Replay this wave's adds element by
-        // element from the shard rows (still unwritten: this wave stores them below), in
+        // element from the shard rows (still unwritten: this wave stores them below; a
+        // chained step replays from RowMap::base, which may be the output itself), in
         // push order, and take the earliest position that left a counter negative (min
         // over positions = first in the reference's order, IntMatrixStore.java:172-176).
         // The push loop is outermost and wave-uniform, so each push's slot of row r is read
@@ -991,7 +1029,8 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
 #pragma unroll
                 for (int c = 0; c < CPW; ++c)
 #pragma unroll
-                    for (int e = 0; e < VEC; ++e) a[c][e] = e < nv[c] ? rowp[r][c0[c] + e] : T(0);
+                    for (int e = 0; e < VEC; ++e)
+                        a[c][e] = e < nv[c] ? (kChainLike ? basep[r][c0[c] + e] : rowp[r][c0[c] + e]) : T(0);
                 for (int b = 0; b < nb; ++b) {
                     const int32_t rrb = __builtin_amdgcn_readlane(vslot[r], b);
                     if (rrb < 0) continue;  // wave-uniform
@@ -1012,7 +1051,7 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
         }
     }
     // every pre-reduce row is written (zeros if no push has it); every chain row (as it arrived)
-    if (MODE == kPreReduce || MODE == kChain) touched = live;
+    if (MODE == kPreReduce || kChainLike) touched = live;
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
         if (!(touched >> r & 1u)) continue;
@@ -1035,7 +1074,7 @@ __global__ __launch_bounds__(64 * WPB, DEPTH == 3 ? kD3Waves : 1) void k_reduce_
             }
         }
     }
-    if (MODE == kAddCheckI32 && negpos != kNoPos) atomicMin(&ctrl->neg_pos, (unsigned long long)negpos);
+    if (kCheck && negpos != kNoPos) atomicMin(&ctrl->neg_pos, (unsigned long long)negpos);
     if (kSpecMode && bad) ctrl->spec_ok = 0u;  // an identity push is not: the host re-runs the chunk
 }
 
@@ -1578,6 +1617,9 @@ __global__ __launch_bounds__(NW * 64) void k_ada_flat(float* __restrict__ shard,
 constexpr unsigned kLdsPerCU = 160 * 1024;
 inline unsigned lds_for_blocks_per_cu(int bpc) { return bpc > 0 ? kLdsPerCU / (unsigned)(bpc + 1) + 256u : 0u; }
 
+// Grid of the int32 rollback: 256 CUs x 8 four-wave blocks; its waves stride over the tasks.
+constexpr int64_t kRollbackBlocks = 2048;
+
 template <typename T, int MODE, int G = 8, bool NT = false, int WPB = 4, int SNT = 0, int CPW = 1, int RPW = 1,
           bool FULL = false>
 static hipError_t launch_reduce_t(void* shard, int64_t rows, int32_t cols, const Batch& bt, int nb,
@@ -1589,7 +1631,8 @@ static hipError_t launch_reduce_t(void* shard, int64_t rows, int32_t cols, const
     const int32_t nchunks = (cols + 64 * VEC - 1) / (64 * VEC);
     const int32_t ngroups = (nchunks + CPW - 1) / CPW;
     const int64_t ntask = (rows + RPW - 1) / RPW * ngroups;
-    const int64_t nblocks = (ntask + WPB - 1) / WPB;
+    int64_t nblocks = (ntask + WPB - 1) / WPB;
+    if constexpr (MODE == kRollbackI32) nblocks = std::min<int64_t>(nblocks, kRollbackBlocks);  // its waves stride
     if (nblocks_out) *nblocks_out = nblocks;
     if (nblocks <= 0) return hipSuccess;
     // blocks per CU: the shape's cap (unused dynamic LDS), 0 = none
@@ -1665,8 +1708,9 @@ static hipError_t launch_auto(void* shard, int64_t rows, int32_t cols, const Bat
                                                      slot, rowflag, ctrl, tail_cut, ada, st, nblocks_out, ev, rm)
 #define DML_LFN(G, CPW, RPW) launch_reduce_t<T, MODE, G, true, 4, 1, CPW, RPW, true>(shard, rows, cols, bt, nb, \
                                                      stride, K, slot, rowflag, ctrl, tail_cut, ada, st, nblocks_out, ev, rm, 0)
-        // (kChain keeps the pre-reduce instantiation's loads and stores of each shape below)
-        if (MODE != kPreReduce && MODE != kChain) {
+        // (kChain and kChainCheckI32 keep the pre-reduce instantiation's loads and stores of
+        // each shape below)
+        if (MODE != kPreReduce && MODE != kChain && MODE != kChainCheckI32) {
             // Rows of >= 4 chunks that do not fill them (config 5's 4000-B int32 rows in
             // 4004-B records): cached record loads (the line two neighbouring records
             // share is fetched once) and 2-wave blocks (a finished block frees its slot
@@ -2067,6 +2111,7 @@ hipError_t launch_reduce(int vtype, int mode, void* shard, int64_t rows, int32_t
         if (mode == kAdd) return DML_A(int32_t, kAdd);
         if (mode == kAddCheckI32) return DML_A(int32_t, kAddCheckI32);
         if (mode == kPreReduce) return DML_A(int32_t, kPreReduce);
+        if (mode == kChainCheckI32) return DML_A(int32_t, kChainCheckI32);
     } else if (vtype == kF64) {
         if (mode == kAdd) return DML_A(double, kAdd);
         if (mode == kPreReduce) return DML_A(double, kPreReduce);
@@ -2078,10 +2123,60 @@ hipError_t launch_reduce(int vtype, int mode, void* shard, int64_t rows, int32_t
 
 hipError_t launch_rollback_i32(int32_t* shard, int64_t rows, int32_t cols, const Batch& bt, int nb,
                                int64_t stride, int K, const int32_t* slot, const uint32_t* rowflag, Ctrl* ctrl,
-                               uint64_t tail_cut, hipStream_t st) {
+                               uint64_t tail_cut, hipStream_t st, RowMap rm) {
     AdaArgs none{};
     return launch_reduce_t<int32_t, kRollbackI32>(shard, rows, cols, bt, nb, stride, K, slot, rowflag, ctrl,
-                                                  tail_cut, none, st, nullptr);
+                                                  tail_cut, none, st, nullptr, LaunchEv{}, rm);
+}
+
+// ---------------------------------------------------------------------------
+// Chained int32 step, after the slice's rollback: one wave, lane 0. Ctrl::neg_pos holds
+// the earliest position at which one of this rank's adds left a counter of the slice
+// negative (kChainCheckI32's atomicMin over every piece of the step), or kNoPos. A set
+// word closes an open record: the position, the key of the record of the push that
+// holds it, the column, the ring step (IllegalStateException(key, col),
+// IntMatrixStore.java:174-176). The word is handed back as kNoPos for the next step.
+__global__ __launch_bounds__(64) void k_chain_i32_verdict(const Batch bt, int nb, int64_t stride, int K,
+                                                          Ctrl* __restrict__ ctrl, ChainI32Rec* __restrict__ rec,
+                                                          int32_t step) {
+    if (threadIdx.x != 0) return;
+    const unsigned long long pos = ctrl->neg_pos;
+    if (pos == kNoPos) return;
+    ctrl->neg_pos = kNoPos;
+    if (rec->pos != kNoPos) return;
+    const int gb = (int)(pos >> 40);
+    const uint64_t off = pos & kOffMask;
+    int b = 0;
+    for (int j = 0; j < nb; ++j) b = bt.bidx[j] == gb ? j : b;
+    const int64_t r = (int64_t)(off / (uint64_t)stride);
+    rec->key = ld_key(bt.base[b] + r * stride, K);
+    rec->col = (int32_t)(((int64_t)off - r * stride - (int64_t)K) / 4);
+    rec->step = step;
+    rec->pad = 0ull;
+    rec->pos = pos;
+}
+
+hipError_t launch_chain_i32_verdict(const Batch& bt, int nb, int64_t stride, int K, Ctrl* ctrl, ChainI32Rec* rec,
+                                    int32_t step, hipStream_t st, LaunchEv ev) {
+    if (ev.start || ev.stop)
+        hipExtLaunchKernelGGL(k_chain_i32_verdict, dim3(1), dim3(64), 0, st, ev.start, ev.stop, 0, bt, nb, stride, K,
+                              ctrl, rec, step);
+    else
+        hipLaunchKernelGGL(k_chain_i32_verdict, dim3(1), dim3(64), 0, st, bt, nb, stride, K, ctrl, rec, step);
+    return hipGetLastError();
+}
+
+// The owner's commit of a chained int32 slice: a closed home record closes the store's
+// record, once (the first verdict stays: the store is in its error state from then on).
+__global__ __launch_bounds__(64) void k_chain_i32_merge(ChainI32Rec* __restrict__ store_rec,
+                                                        const ChainI32Rec* __restrict__ home) {
+    if (threadIdx.x != 0) return;
+    if (store_rec->pos == kNoPos && home->pos != kNoPos) *store_rec = *home;
+}
+
+hipError_t launch_chain_i32_merge(ChainI32Rec* store_rec, const ChainI32Rec* home, hipStream_t st) {
+    hipLaunchKernelGGL(k_chain_i32_merge, dim3(1), dim3(64), 0, st, store_rec, home);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------

@@ -273,6 +273,12 @@ struct dml_store {
     unsigned long long* neg_host = nullptr;  // pinned copy, DMA'd behind every checked apply
     hipEvent_t neg_ev = nullptr;
     bool neg_pending = false;
+    // int32 chained commits (dml_store_assign_dense_i32_device): the sticky closed record
+    // (open = pos kNoPos; step 0 of every chained call seeds its slice's record from it)
+    ChainI32Rec* crec_dev = nullptr;
+    ChainI32Rec* crec_host = nullptr;  // pinned copy, DMA'd behind every commit
+    hipEvent_t crec_ev = nullptr;
+    bool crec_pending = false;
     // timing of the dominant kernel
     const char* kname = nullptr;  // its instantiation, as last launched (dml_store_kernel_name)
     bool timing = false;
@@ -1024,7 +1030,28 @@ int check_store(dml_store* s) {
 // Result of the int32 owner applies (dml_store_apply_dense_device): the first
 // negative counter becomes the store's IllegalStateException. `block` waits for
 // the last apply; otherwise only a finished one is read.
+int collect_chain_check(dml_store* s, bool block) {
+    if (!s->crec_pending) return DML_OK;
+    if (!block && hipEventQuery(s->crec_ev) == hipErrorNotReady) return DML_OK;
+    HIPCHK(hipEventSynchronize(s->crec_ev));
+    s->crec_pending = false;
+    const ChainI32Rec r = *s->crec_host;
+    if (r.pos == kNoPos) return DML_OK;
+    return record_error(s, DML_E_NEGATIVE_COUNTER, (int64_t)r.key, r.col);
+}
+
+int ensure_chain_record(dml_store* s) {
+    if (s->crec_dev) return DML_OK;
+    HIPCHK(hipMalloc((void**)&s->crec_dev, sizeof(ChainI32Rec)));
+    HIPCHK(hipMemsetAsync(s->crec_dev, 0xFF, sizeof(ChainI32Rec), s->stream));
+    HIPCHK(hipHostMalloc((void**)&s->crec_host, sizeof(ChainI32Rec), hipHostMallocDefault));
+    HIPCHK(hipEventCreateWithFlags(&s->crec_ev, hipEventDisableTiming));
+    return DML_OK;
+}
+
 int collect_apply_check(dml_store* s, bool block) {
+    // a chained int32 commit that brought a closed record home (finished, or waited for)
+    if (int rc = collect_chain_check(s, block)) return rc;
     if (!s->neg_pending) return DML_OK;
     if (!block && hipEventQuery(s->neg_ev) == hipErrorNotReady) return DML_OK;
     HIPCHK(hipEventSynchronize(s->neg_ev));
@@ -1065,6 +1092,26 @@ int store_assign_adagrad(dml_store* s, int64_t row0, int64_t nrows, const void* 
     HIPCHK(launch_chain_ada_commit((float*)s->data + e0, s->delta + e0, s->alpha + e0, rec ? s->md : nullptr,
                                    (const float*)data, (const float*)delta, (const uint32_t*)marks,
                                    (const MaxDelta*)rec, nrows, s->cols, ada_args(s), s->stream));
+    return DML_OK;
+}
+
+int store_chain_i32_record(dml_store* s, void** dev_rec) {
+    if (int rc = check_store(s)) return rc;
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceGuard g(s->device);
+    if (!s->is_matrix || s->adagrad || !s->desc.dense_column || vtype_of(s->desc) != kI32)
+        return set_err(DML_E_UNSUPPORTED, "not a dense int32 matrix store");
+    if (int rc = ensure_chain_record(s)) return rc;
+    *dev_rec = s->crec_dev;
+    return DML_OK;
+}
+
+int store_chain_i32_collect(dml_store* s, bool block) {
+    if (int rc = check_store(s)) return rc;
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceGuard g(s->device);
+    if (int rc = collect_chain_check(s, block)) return rc;
+    if (s->err) return set_err(s->err, "store is in a failed state (see dml_store_error_state)");
     return DML_OK;
 }
 
@@ -1220,6 +1267,9 @@ void dml_store_destroy(dml_store* s) {
         (void)hipFree(s->cand);
         (void)hipFree(s->md);
         (void)hipFree(s->neg_dev);
+        (void)hipFree(s->crec_dev);
+        if (s->crec_host) (void)hipHostFree(s->crec_host);
+        if (s->crec_ev) (void)hipEventDestroy(s->crec_ev);
         if (s->neg_host) (void)hipHostFree(s->neg_host);
         if (s->neg_ev) (void)hipEventDestroy(s->neg_ev);
         (void)hipFree(s->dstage);
@@ -1361,6 +1411,13 @@ void dml_store_clear_error(dml_store* s) {
     s->err = 0;
     s->err_key = 0;
     s->err_col = -1;
+    if (s->crec_dev) {  // chained int32 calls resume: the record is open again
+        DeviceGuard g(s->device);
+        (void)hipStreamSynchronize(s->stream);
+        s->crec_pending = false;
+        (void)hipMemsetAsync(s->crec_dev, 0xFF, sizeof(ChainI32Rec), s->stream);
+        (void)hipStreamSynchronize(s->stream);
+    }
     if (s->neg_dev) {  // int32 owner applies resume
         DeviceGuard g(s->device);
         (void)hipStreamSynchronize(s->stream);
@@ -1780,6 +1837,28 @@ int dml_store_assign_dense_device(dml_store* s, const void* dev_src, int64_t ele
     return DML_OK;
 }
 
+int dml_store_assign_dense_i32_device(dml_store* s, const void* dev_src, int64_t elems, const void* dev_record) {
+    if (int rc = check_store(s)) return rc;
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceGuard g(s->device);
+    if (!s->is_matrix || s->adagrad || !s->desc.dense_column || vtype_of(s->desc) != kI32)
+        return set_err(DML_E_UNSUPPORTED,
+                       "assign with a verdict record: dense int32 matrices (fp32 / fp64: dml_store_assign_dense_device)");
+    if (int rc = retire_all(s)) return rc;
+    if (int rc = collect_apply_check(s, false)) return rc;
+    if (s->err) return set_err(s->err, "store is in a failed state (see dml_store_error_state)");
+    if (!dev_src || !dev_record || elems != s->rows * s->cols) return set_err(DML_E_INVALID_ARG, "assign size mismatch");
+    if ((uintptr_t)dev_record & 7u) return set_err(DML_E_INVALID_ARG, "verdict record is not 8-byte aligned");
+    if (int rc = ensure_chain_record(s)) return rc;
+    // the slice as it came home: a closed one holds the adds up to the failing one
+    HIPCHK(hipMemcpyAsync(s->data, dev_src, (size_t)elems * (size_t)s->V, hipMemcpyDeviceToDevice, s->stream));
+    HIPCHK(launch_chain_i32_merge(s->crec_dev, (const ChainI32Rec*)dev_record, s->stream));
+    HIPCHK(hipMemcpyAsync(s->crec_host, s->crec_dev, sizeof(ChainI32Rec), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipEventRecord(s->crec_ev, s->stream));
+    s->crec_pending = true;
+    return DML_OK;
+}
+
 int dml_store_assign_adagrad_device(dml_store* s, const void* dev_data, const void* dev_delta, const void* dev_marks,
                                     const void* dev_maxdelta_record) {
     if (int rc = check_store(s)) return rc;
@@ -1994,6 +2073,7 @@ struct dml_prereduce {
     const Ctrl* hidx = nullptr;  // the workspace's Ctrl as the index left it (speculative calls of the flat shape)
     bool chain_checked = false;  // the first chain piece decided about the up-front identity check
     bool slots_unread = false;   // that check ran after the index: the pieces leave the filled slot table as it is
+    bool slots_kept = false;     // int32 chain pieces ran: they keep the table for the step's rollback
     std::vector<CandBuf> cands;  // AdaGrad chain pieces: maxDelta candidates (the last is current), back to the pool at _end
 };
 
@@ -2260,7 +2340,7 @@ struct AdaPiece {
 };
 static int prereduce_piece(dml_prereduce* p, int mode, int64_t row_block, int64_t row_stride, int64_t row_off,
                            int64_t ntask_rows, const void* dev_base, void* dev_out, void* stream,
-                           const AdaPiece* ap = nullptr) {
+                           const AdaPiece* ap = nullptr, const void* dev_record = nullptr) {
     hipStream_t st = (hipStream_t)stream;  // as given: 0 is HIP's null stream
     if (mode == kChain && !p->chain_checked) {
         // Ascending full-range pushes of a flat shape (config 4's case): verify every
@@ -2296,6 +2376,8 @@ static int prereduce_piece(dml_prereduce* p, int mode, int64_t row_block, int64_
     rm.rows_total = p->rows;
     rm.out = dev_out;
     rm.base = dev_base;
+    rm.rec = dev_record;
+    if (mode == kChainCheckI32) p->slots_kept = true;
     AdaArgs none{};
     if (!p->last_ev) HIPCHK(hipEventCreateWithFlags(&p->last_ev, hipEventDisableTiming));
     // the piece's completion event rides in its dispatch packet (no marker packet between pieces)
@@ -2401,6 +2483,75 @@ int dml_prereduce_chain_piece_ada(dml_prereduce* p, int64_t row_block, int64_t r
     return prereduce_piece(p, kChain, row_block, row_stride, row_off, ntask_rows, base_data, out_data, stream, &ap);
 }
 
+static int chain_i32_refusal(const dml_prereduce* p) {
+    if (p->desc.ada_grad || p->desc.value_type != DML_ELEMENT_TYPE_INT)
+        return set_err(DML_E_UNSUPPORTED,
+                       "int32 chained pieces: a dense int32 matrix handle (fp32 / fp64: dml_prereduce_chain_piece; "
+                       "AdaGrad: dml_prereduce_chain_piece_ada)");
+    // the slice leaves the rank right after the step's close: a speculative handle's
+    // verdict (dml_prereduce_verify) would come later
+    if (p->ctx) return set_err(DML_E_UNSUPPORTED, "chained pieces need dml_prereduce_begin (no speculative context)");
+    return DML_OK;
+}
+
+int dml_prereduce_chain_piece_i32(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
+                                  int64_t ntask_rows, const void* dev_base, void* dev_out, const void* dev_record,
+                                  void* stream) {
+    if (!p || !dev_base || !dev_out || !dev_record || ((uintptr_t)dev_record & 7u) || row_block <= 0 || ntask_rows < 0)
+        return set_err(DML_E_INVALID_ARG, "bad int32 chain piece arguments");
+    if (int rc = chain_i32_refusal(p)) return rc;
+    return prereduce_piece(p, kChainCheckI32, row_block, row_stride, row_off, ntask_rows, dev_base, dev_out, stream,
+                           nullptr, dev_record);
+}
+
+int dml_prereduce_chain_close_i32(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
+                                  int64_t ntask_rows, void* dev_slice, void* dev_record, int32_t ring_step,
+                                  void* stream) {
+    if (!p || !dev_slice || !dev_record || ((uintptr_t)dev_record & 7u) || row_block <= 0 || ntask_rows < 0 ||
+        ring_step < 0)
+        return set_err(DML_E_INVALID_ARG, "bad int32 chain close arguments");
+    if (int rc = chain_i32_refusal(p)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (st != p->stream && !p->idx_waited) {
+        HIPCHK(hipEventSynchronize(p->idx_ev));
+        p->idx_waited = true;
+    }
+    RowMap rm;
+    rm.block = row_block;
+    rm.stride = row_stride;
+    rm.off = row_off;
+    rm.rows_total = p->rows;
+    rm.out = dev_slice;
+    if (!p->last_ev) HIPCHK(hipEventCreateWithFlags(&p->last_ev, hipEventDisableTiming));
+    LaunchEv ev{nullptr, p->last_ev};
+    if (p->timed) {
+        std::pair<hipEvent_t, hipEvent_t> t{nullptr, nullptr};
+        {
+            std::lock_guard<std::mutex> lk(g_pre_mu);
+            if (!g_pre_pool.empty()) {
+                t = g_pre_pool.back();
+                g_pre_pool.pop_back();
+            }
+        }
+        if (!t.first) {
+            HIPCHK(hipEventCreate(&t.first));
+            HIPCHK(hipEventCreate(&t.second));
+        }
+        p->tev.push_back(t);
+        HIPCHK(hipEventRecord(t.first, st));
+        ev.stop = t.second;
+    }
+    // undo, mod 2^32, this rank's adds past the step's first negative (waves leave at
+    // once while Ctrl::neg_pos is kNoPos), then the verdict: one launch each per step
+    if (ntask_rows > 0 && p->nb > 0)
+        HIPCHK(launch_rollback_i32((int32_t*)dev_slice, ntask_rows, p->cols, p->bt, p->nb, p->stride, p->K, p->slot,
+                                   nullptr, p->ctrl, kNoPos, st, rm));
+    HIPCHK(launch_chain_i32_verdict(p->bt, p->nb, p->stride, p->K, p->ctrl, (ChainI32Rec*)dev_record, ring_step, st, ev));
+    p->done_ev = ev.stop;
+    p->last_st = st;
+    return DML_OK;
+}
+
 int dml_prereduce_timing(int32_t every) {
     g_pre_timing.store(every > 0 ? every : 0);
     g_pre_calls.store(0);
@@ -2499,7 +2650,7 @@ int dml_prereduce_end(dml_prereduce* p) {
     // slots unread and uncleared; pushes it rejected were read and cleared like any other)
     const uint64_t pushes = p->nb >= 64 ? ~0ull : (1ull << p->nb) - 1ull;
     if (p->slots_unread && !(h.ident & pushes)) p->slots_unread = false;
-    const bool clean = rc == DML_OK && !p->slots_unread && p->rows_done == p->rows &&
+    const bool clean = rc == DML_OK && !p->slots_unread && !p->slots_kept && p->rows_done == p->rows &&
                        reduce_clears_slots(p->desc.value_type, kPreReduce, p->cols);
     if (e == hipSuccess) ws_release(p->device, WsLease{p->ws, p->ws_bytes, clean, p->hctrl, p->rows});
     if (e == hipSuccess) cand_release(p->device, p->cands);

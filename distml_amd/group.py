@@ -29,7 +29,10 @@ The order-exact chained reduce-scatter (dml_group_push_chained) i
 bound by NativeShardGroup.push_chained only — the native group is the one the JNI
 deploys; this torch ShardGroup has no chained path. HipOps.chain_piece and
 HipOps.assign expose its two building blocks, HipOps.chain_piece_ada and
-HipOps.assign_ada those of AdaGrad matrices.
+HipOps.assign_ada those of AdaGrad matrices. Dense int32 matrices have the same ring
+under NativeShardGroup.push_chained_i32 (dml_group_push_chained_i32: every add checked,
+a verdict record per slice), built from HipOps.chain_piece_i32, chain_close_i32 and
+assign_i32.
 
 Buffer contract of the asynchronous paths (push_full_range, push_exchange,
 push_local): the push buffers must stay allocated and unmodified until flush()
@@ -46,6 +49,7 @@ from .datadesc import DataDesc, KeyRange
 from .store import DataStore, check
 
 
+CHAIN_I32_RECORD_BYTES = 32  # DML_CHAIN_I32_RECORD_BYTES: [u64 pos][i64 key][i32 col][i32 ring step][u64 pad]; open = pos all ones
 MAXDELTA_RECORD_BYTES = 32  # DML_MAXDELTA_RECORD_BYTES: [f32 value][i32 row][i32 col][pad][pending candidate]
 
 
@@ -107,6 +111,29 @@ class HipOps:
         maxDelta = the record's."""
         check(_lib.load().dml_store_assign_adagrad_device(store._h, C.c_void_p(data_ptr), C.c_void_p(delta_ptr),
                                                           C.c_void_p(marks_ptr), C.c_void_p(record_ptr)), store)
+
+    def chain_piece_i32(self, h, block: int, stride: int, off: int, ntask_rows: int, base_ptr: int, out_ptr: int,
+                        record_ptr: int, stream: int) -> None:
+        """One piece of a chained int32 ring step (dml_prereduce_chain_piece_i32): out = base +
+        the handle's pushes' rows, every add checked; a slice whose record (CHAIN_I32_RECORD_BYTES,
+        device memory) arrived closed is copied. chain_close_i32 must follow the step's pieces."""
+        check(_lib.load().dml_prereduce_chain_piece_i32(C.c_void_p(h), block, stride, off, ntask_rows,
+                                                        C.c_void_p(base_ptr), C.c_void_p(out_ptr),
+                                                        C.c_void_p(record_ptr), C.c_void_p(stream)))
+
+    def chain_close_i32(self, h, block: int, stride: int, off: int, ntask_rows: int, slice_ptr: int, record_ptr: int,
+                        ring_step: int, stream: int) -> None:
+        """The step's verdict over the whole slice (dml_prereduce_chain_close_i32): the handle's
+        adds past the step's first negative are undone in place and an open record is closed."""
+        check(_lib.load().dml_prereduce_chain_close_i32(C.c_void_p(h), block, stride, off, ntask_rows,
+                                                        C.c_void_p(slice_ptr), C.c_void_p(record_ptr), ring_step,
+                                                        C.c_void_p(stream)))
+
+    def assign_i32(self, store: DataStore, src_ptr: int, elems: int, record_ptr: int) -> None:
+        """The owner's commit of a chained int32 slice (dml_store_assign_dense_i32_device): shard =
+        src; a closed record puts the store into its error state when it next retires that work."""
+        check(_lib.load().dml_store_assign_dense_i32_device(store._h, C.c_void_p(src_ptr), elems,
+                                                            C.c_void_p(record_ptr)), store)
 
     def end(self, h) -> None:
         check(_lib.load().dml_prereduce_end(C.c_void_p(h)))
@@ -741,6 +768,16 @@ class NativeShardGroup:
         ptrs = (C.c_void_p * max(n, 1))(*dev_ptrs)
         ls = (C.c_int64 * max(n, 1))(*lens)
         check(self._L.dml_group_push_chained(C.c_void_p(self._h), ptrs, ls, n), self.store)
+
+    def push_chained_i32(self, dev_ptrs: Sequence[int], lens: Sequence[int]) -> None:
+        """The chained reduce-scatter of a dense int32 matrix (dml_group_push_chained_i32): shard s
+        ends equal to one IntMatrixStore fed rank s's pushes, then rank s+1's, ..., every add
+        checked. Only the owner of a shard that closed raises (IllegalStateException: negative
+        counter), from its next call or flush()."""
+        n = len(dev_ptrs)
+        ptrs = (C.c_void_p * max(n, 1))(*dev_ptrs)
+        ls = (C.c_int64 * max(n, 1))(*lens)
+        check(self._L.dml_group_push_chained_i32(C.c_void_p(self._h), ptrs, ls, n), self.store)
 
     def debug_fail_verify(self, nth: int) -> None:
         """Fault injection (tests): the nth full-range call finished from now fails its verdict."""

@@ -308,6 +308,25 @@ int dml_store_assign_dense_device(dml_store* s, const void* dev_src, int64_t ele
 #define DML_MAXDELTA_RECORD_BYTES 32
 int dml_store_assign_adagrad_device(dml_store* s, const void* dev_data, const void* dev_delta, const void* dev_marks,
                                     const void* dev_maxdelta_record);
+/* The owner's commit of a chained int32 slice (dml_group_push_chained_i32), on
+ * the store's stream, ordered like dml_store_assign_dense_device: shard =
+ * dev_src, and the slice's verdict record (DML_CHAIN_I32_RECORD_BYTES, 8-byte
+ * aligned, device memory) is merged into the store's own device-resident record:
+ * the first closed record to come home stays. The store's record is then copied
+ * to pinned host memory; when the store next retires that work (a read,
+ * dml_store_flush, a later push once the copy has finished) a closed record puts
+ * it into its usual error state: sticky DML_E_NEGATIVE_COUNTER with the record's
+ * key and col from dml_store_error_state, later pushes refused
+ * (IntMatrixStore.java:174-176, PSAgent.java:188-191). A closed slice holds every
+ * add up to and including the failing one and nothing after it, so the
+ * assignment leaves what the reference's store holds when its exception escapes.
+ * Dense int32 matrices only; other stores: DML_E_UNSUPPORTED. Both buffers are
+ * read on the store's stream: keep them until that stream has passed the commit.
+ * The record: [u64 pos][i64 key][i32 col][i32 ring step][u64 pad]; pos is all
+ * ones while the slice is open, otherwise (push << 40) | byte offset of the
+ * failing add in the closing rank's push. */
+#define DML_CHAIN_I32_RECORD_BYTES 32
+int dml_store_assign_dense_i32_device(dml_store* s, const void* dev_src, int64_t elems, const void* dev_record);
 /* Two-moment AdaGrad owner apply: dev_src holds rows x [cols Σu |
  * cols Σu²] f32 (the reduce-scattered dml_prereduce_moments_piece output of the
  * shard's rows); data += Σu, delta += Σu², alpha = initialAlpha / (factor *
@@ -398,6 +417,37 @@ int dml_prereduce_chain_piece_ada(dml_prereduce* p, int64_t row_block, int64_t r
                                   int64_t ntask_rows, const void* base_data, const void* base_delta,
                                   const void* base_marks, void* out_data, void* out_delta, void* out_marks,
                                   void* maxdelta_record, int32_t last_piece, void* stream);
+/* One piece of a ring step of the chained reduce-scatter of a dense int32 matrix
+ * (IntMatrixStore, LightLDA's word-topic counts). Row map, stream rule, host
+ * wait and completion event as dml_prereduce_chain_piece. Task row t starts
+ * from dev_base + t*cols; the handle's pushes' records of its model row are
+ * added in push order, each add wrapping mod 2^32 and checked: the earliest
+ * position (push << 40 | byte offset) whose add left a counter negative is kept
+ * in the handle's control block (an atomic minimum over every piece of the
+ * step). Every add is made; dml_prereduce_chain_close_i32 undoes the later ones
+ * once all pieces of the step have run. The row is written to dev_out + t*cols;
+ * dev_out == dev_base works. Copied bit for bit, nothing added: every row when
+ * dev_record (the slice's verdict record, DML_CHAIN_I32_RECORD_BYTES, 8-byte
+ * aligned, read only) arrived closed; every row when the handle's index found a
+ * key outside the matrix or a row listed twice in one push (_end reports it);
+ * a row no push lists; a padding row.
+ * DML_E_UNSUPPORTED for handles that are not dense int32 matrices and for a
+ * speculative context's handle. */
+int dml_prereduce_chain_piece_i32(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
+                                  int64_t ntask_rows, const void* dev_base, void* dev_out, const void* dev_record,
+                                  void* stream);
+/* Closes the ring step its _piece_i32 calls made on `stream`: the row map is the
+ * whole slice's (dev_slice + t*cols holds task row t, every row some piece of
+ * the step wrote). One rollback launch undoes, mod 2^32 and in place, every add
+ * of this handle past the step's first negative position (its waves leave at
+ * once when there is none); then a one-wave kernel closes an open record with
+ * that position, the key of the record that holds it, the column and ring_step
+ * (IllegalStateException(key, col), IntMatrixStore.java:174-176), and hands the
+ * control block's word back clear. The slice then holds every add up to and
+ * including the failing one and nothing after it, and may leave the rank. */
+int dml_prereduce_chain_close_i32(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
+                                  int64_t ntask_rows, void* dev_slice, void* dev_record, int32_t ring_step,
+                                  void* stream);
 /* The two-moment piece of an AdaGrad matrix's pre-reduce (begun with its desc):
  * task row t's Σu and Σu·u over the pushes, in push order, written as
  * dev_out + t*2*cols = [cols Σu | cols Σu²] (f32; rows of whole 16-B vectors
@@ -562,6 +612,32 @@ int dml_group_push_local(dml_group* g, const void* const* dev_bufs, const int64_
  * DML_E_UNSUPPORTED (use dml_group_push_exchange), on every rank alike and
  * before any send. */
 int dml_group_push_chained(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n);
+/* The chained reduce-scatter for dense int32 matrices (IntMatrixStore): same
+ * arguments, ring, buffers, call order and failed-rank rule as
+ * dml_group_push_chained. After the call shard s equals one IntMatrixStore over
+ * shard s's keys fed rank s's pushes, then rank s+1's, ..., then rank s-1's,
+ * each in push order (IntMatrixStore.java:154-178): every add wraps mod 2^32 and
+ * is checked; at the first counter left negative the shard holds every add up
+ * to and including that one and nothing after it, and it is closed: it takes no
+ * add from any rank in this call or any later one (PSAgent.java:188-191). The
+ * other shards go on. Each slice carries a verdict record
+ * (DML_CHAIN_I32_RECORD_BYTES) at the head of its first sub-chunk's message, so
+ * S + N * 32 bytes per rank cross xGMI. No sub-chunk of a slice leaves a rank
+ * before the rank's whole step over the slice has its verdict
+ * (dml_prereduce_chain_close_i32), so piece time does not hide under the step's
+ * own transfers as it does for floats.
+ * Who reports: only the owner of a closed shard, through its next group call or
+ * dml_group_flush: DML_E_NEGATIVE_COUNTER, key and col from
+ * dml_store_error_state; a non-chained call (push_local, push_exchange,
+ * push_full_range) right behind the closing call waits for the commit's record
+ * and is refused as the reference refuses it; the next chained call does not
+ * wait (the store's device-resident record already keeps the shard closed) and
+ * reports once the host has seen the record. The owner's pushes still reach the
+ * other shards. The other ranks return DML_OK.
+ * At world 1 the call is dml_store_push_batch_device. Any group that is not a
+ * dense int32 matrix: DML_E_UNSUPPORTED, on every rank alike and before any
+ * send. */
+int dml_group_push_chained_i32(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n);
 int dml_group_flush(dml_group* g);
 void dml_group_destroy(dml_group* g);
 /* Fault injection for tests: the nth full-range call finished from now on (1 = the

@@ -58,6 +58,17 @@ public class GpuShardGroup implements AutoCloseable {
      */
     public void pushChained(long[] devPtrs, long[] lens) { nativeGroupPush(handle, devPtrs, lens, 4); }
 
+    /**
+     * The chained path for dense int matrices (IntMatrixStore, LightLDA's word-topic counts):
+     * shard s ends equal to one IntMatrixStore fed rank s's pushes, then rank s+1's, ..., every
+     * add checked (IntMatrixStore.java:154-178). A shard whose counter went negative holds the
+     * adds up to that one, is closed for good, and its owner's next call or flush() throws the
+     * IllegalStateException with the key and column; the other ranks' calls return normally
+     * and the other shards go on. Other formats throw a RuntimeException naming pushChained's
+     * native call.
+     */
+    public void pushChainedChecked(long[] devPtrs, long[] lens) { nativeGroupPush(handle, devPtrs, lens, 5); }
+
     /** Every call applied; throws the first deferred key / repeated-row error. */
     public void flush() { nativeGroupFlush(handle); }
 

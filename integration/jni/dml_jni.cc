@@ -327,7 +327,8 @@ JNIEXPORT jlong JNICALL GFN(nativeGroupCreate)(JNIEnv* env, jclass, jbyteArray i
 }
 
 // mode: 0 full-range pre-reduce, 1 exact exchange, 2 two-moment AdaGrad, 3 local (already split),
-// 4 order-exact chained reduce-scatter (fp32 / fp64, plain or AdaGrad)
+// 4 order-exact chained reduce-scatter (fp32 / fp64, plain or AdaGrad), 5 the same for dense int32
+// matrices, every add checked (dml_group_push_chained_i32)
 JNIEXPORT void JNICALL GFN(nativeGroupPush)(JNIEnv* env, jclass, jlong g, jlongArray ptrs, jlongArray lens,
                                              jint mode) {
     const jsize n = env->GetArrayLength(ptrs);
@@ -347,6 +348,7 @@ JNIEXPORT void JNICALL GFN(nativeGroupPush)(JNIEnv* env, jclass, jlong g, jlongA
         case 2: rc = dml_group_push_moments(G(g), dp.data(), dl.data(), (int32_t)n); break;
         case 3: rc = dml_group_push_local(G(g), dp.data(), dl.data(), (int32_t)n); break;
         case 4: rc = dml_group_push_chained(G(g), dp.data(), dl.data(), (int32_t)n); break;
+        case 5: rc = dml_group_push_chained_i32(G(g), dp.data(), dl.data(), (int32_t)n); break;
         default: break;
     }
     if (rc) throw_for(env, rc);
