@@ -2210,6 +2210,12 @@ __global__ __launch_bounds__(256) void k_maxdelta(const DeltaCand* __restrict__ 
                                                   MaxDelta* __restrict__ md, const Batch bt, int nb,
                                                   int64_t stride, int K, int V, int mode,
                                                   const Ctrl* __restrict__ ctrl) {
+    // A chunk behind an abnormal predecessor ran as a no-op (the host relaunches or drops
+    // it): its blocks wrote no candidate, and a pending one is the predecessor's (a chunk
+    // with a repeated row defers its finalize to its replay), positioned in that chunk's
+    // pushes. Resolving it against this chunk's table read a record of the wrong buffer,
+    // past its end when this chunk's push was shorter, and cleared what the replay needs.
+    if (bt.prev && ctrl_abnormal(bt.prev)) return;
     bool ok = false;
     float v = 0.f;
     uint64_t p = kNoPos;

@@ -1562,10 +1562,11 @@ static int fetch_impl(dml_store* s, const int64_t* keys, int64_t nkeys, int64_t 
     *out_len = nkeys * rec;
     if (!out || cap < *out_len) return set_err(DML_E_CAPACITY, "fetch output buffer too small");
     if (keys) {
-        for (int64_t j = 0; j < nkeys; ++j) {
-            const int32_t idx = (int32_t)(uint32_t)((uint64_t)keys[j] - (uint64_t)s->first);
-            if (idx < 0 || idx >= s->rows) return record_error(s, DML_E_KEY_OUT_OF_SHARD, keys[j], -1);
-        }
+        // by range, not by indexOf's narrowed (int)(key - first): the reference intersects a
+        // fetch's keys with the shard before any indexOf (FloatMatrixStore.java:116,
+        // KeyList.java:74-86), and k_fetch indexes with the 64-bit key - first
+        for (int64_t j = 0; j < nkeys; ++j)
+            if (keys[j] < s->first || keys[j] > s->last) return record_error(s, DML_E_KEY_OUT_OF_SHARD, keys[j], -1);
     }
     if (nkeys == 0) return DML_OK;
     const size_t kbytes = keys ? ((size_t)nkeys * 8 + 255) & ~(size_t)255 : 0;

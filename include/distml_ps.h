@@ -223,7 +223,9 @@ int dml_store_max_delta(dml_store* s, float* max_delta, int32_t* row, int32_t* c
  * IntMatrixStore.java:81-140, FloatArrayStore.java:88-108, IntArrayStore.java:78-95,
  * DoubleArrayStore.java handleFetch, FloatMatrixStoreAdaGrad.java:146-213).
  * `keys` are the intersected keys in the caller's iteration order; every key
- * must lie in the shard. Writes the reference byte layout to `out`. */
+ * must lie in the shard. Writes the reference byte layout to `out`.
+ * The check is by range (first <= key <= last as 64-bit values), not by indexOf's narrowed
+ * index: any other key is refused with DML_E_KEY_OUT_OF_SHARD before anything is copied. */
 int dml_store_fetch(dml_store* s, const int64_t* keys, int64_t nkeys,
                     uint8_t* out, int64_t cap, int64_t* out_len);
 /* Same for a KeyRange request: keys first..last ascending (KeyRange.intersect). */

@@ -139,6 +139,7 @@ int orc_error(const orc_store* s, int64_t* key, int32_t* col) {
     if (col) *col = s->err_col;
     return s->err;
 }
+void orc_clear_error(orc_store* s) { s->err = 0; s->err_key = 0; s->err_col = 0; }
 
 /* setAlpha (FloatMatrixStoreAdaGrad.java:77-82, setAlphaValue :96-106). */
 void orc_set_alpha(orc_store* s, float initial_alpha, float min_alpha, float factor) {

@@ -51,6 +51,8 @@ float* orc_delta(orc_store* s);
 
 int orc_push(orc_store* s, const uint8_t* data, int64_t len);
 int orc_error(const orc_store* s, int64_t* key, int32_t* col);
+/* Forget the recorded error (dml_store_clear_error's counterpart): the next failing push records anew. */
+void orc_clear_error(orc_store* s);
 void orc_set_alpha(orc_store* s, float initial_alpha, float min_alpha, float factor);
 void orc_max_delta(const orc_store* s, float* v, int32_t* row, int32_t* col);
 

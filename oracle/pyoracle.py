@@ -49,6 +49,7 @@ def lib():
         L.orc_push_many.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(i64), i32, i32]
         L.orc_error.restype = C.c_int
         L.orc_error.argtypes = [vp, C.POINTER(i64), C.POINTER(i32)]
+        L.orc_clear_error.argtypes = [vp]
         L.orc_set_alpha.argtypes = [vp, C.c_float, C.c_float, C.c_float]
         L.orc_max_delta.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i32), C.POINTER(i32)]
         L.orc_fetch.restype = i64
@@ -130,6 +131,9 @@ class OracleStore:
         k, c = C.c_int64(), C.c_int32()
         code = lib().orc_error(self._h, C.byref(k), C.byref(c))
         return code, k.value, c.value
+
+    def clear_error(self):
+        lib().orc_clear_error(self._h)
 
     def set_alpha(self, initial, minimum, factor):
         lib().orc_set_alpha(self._h, initial, minimum, factor)

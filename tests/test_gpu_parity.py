@@ -1902,6 +1902,38 @@ def test_adagrad_maxdelta_tie_repeated_row(oracle, batched):
     assert kat.bits_equal(s.values(), o.data)
 
 
+def test_adagrad_maxdelta_pending_behind_repeated_row(oracle):
+    """Two device calls in flight. The first lists row 5 twice, so its maxDelta finalize
+    waits for the host's replay with the candidate of row 2 (delta 9.0 at its record 0)
+    pending; the second ran as a no-op behind it and is relaunched after the replay. Its
+    finalize must leave the pending candidate alone: resolved against the second call's
+    pushes, record 0 is row 1, not row 2 (found by tests/test_gpu_opseq.py, ada_c48 seed 6,
+    where the second call's push was shorter than the position it was read at)."""
+    from distml_amd import DataDesc, DataStore, KeyRange, encode_matrix_push
+    rows, cols = 8, 4
+    fmt = DataDesc(1, 0, 1, False, True, True)
+    s = DataStore(fmt, KeyRange(0, rows - 1), cols, async_push=True)
+    o = oracle_store(oracle, fmt, 0, rows - 1, cols)
+    s.setAlpha(0.025, 0.0001, 1.5)
+    o.set_alpha(0.025, 0.0001, 1.5)
+    g = np.zeros((3, cols), np.float32)
+    g[0, 1], g[1, 0], g[2, 0] = 3.0, 1.0, 1.0
+    p1 = encode_matrix_push([2, 5, 5], g, 0, 1)
+    p2 = encode_matrix_push([1, 3, 4], np.full((3, cols), 0.5, np.float32), 0, 1)  # as long as p1
+    dev = [torch.frombuffer(bytearray(p), dtype=torch.uint8).cuda() for p in (p1, p2)]
+    torch.cuda.synchronize()
+    for d, p in zip(dev, (p1, p2)):
+        s.pushDevice([d.data_ptr()], [d.numel()])
+        assert o.push(p) == 0
+    s.flush()
+    assert o.max_delta() == (9.0, 2, 1)
+    assert s.maxDelta() == o.max_delta()
+    assert kat.bits_equal(s.values(), o.data)
+    a, d = s.adagrad_state()
+    assert kat.bits_equal(a, o.alpha) and kat.bits_equal(d, o.delta)
+    s.close()
+
+
 @pytest.mark.parametrize("case", ["hot_line", "cutoff", "truncated", "push_repeat", "f64"])
 def test_sparse_single_pass_partition_exact(oracle, case):
     """The single-pass sparse partition (fixed-capacity bins, atomic cursors; DESIGN.md
