@@ -20,16 +20,13 @@
 // at dml_group_flush. The communicator comes from ncclCommInitRankConfig (the
 // channel count pinned, kRsChannels) with a unique id the caller distributes (the
 // JVM's control plane).
-// dml_group_push_chained is the order-exact alternative for plain fp32 / fp64
-// matrices and for AdaGrad matrices: each shard's slice walks the ring of ranks over
-// ncclSend / ncclRecv and every rank adds its own pushes' rows to it in push order
-// (DESIGN.md §6). An AdaGrad slice carries data, delta, a touched mark per row and
-// the maxDelta record; the owner computes alpha once at its commit. One documented
-// divergence there (the alpha of an element whose delta comes home NaN, DESIGN.md
-// §2); dml_group_push_exchange is the path without it.
-// dml_group_push_chained_i32 is the same ring for dense int32 matrices (IntMatrixStore):
-// every slice carries a 32-byte verdict record, every add is checked, and no sub-chunk
-// leaves a rank before the rank's whole step over the slice has its verdict.
+// dml_group_push_chained (plain fp32 / fp64 and AdaGrad matrices) and
+// dml_group_push_chained_i32 (dense int32, IntMatrixStore) are the order-exact alternative:
+// each shard's slice walks the ring of ranks over ncclSend / ncclRecv and every rank adds its
+// own pushes' rows to it in push order. One driver, chain_push, runs the ring
+// for all three kinds of slice; what a kind carries and checks is described at ChainKind. One
+// documented divergence (AdaGrad: the alpha of an element whose delta comes home NaN,
+// DESIGN.md §2); dml_group_push_exchange is the path without it.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -116,10 +113,10 @@ struct dml_group {
     hipEvent_t mapplied[2] = {nullptr, nullptr};
     std::deque<dml_prereduce*> mpending;  // calls whose index errors are not yet collected
     int mk = 0;
-    // chained path (dml_group_push_chained), allocated on its first call: two buffer
-    // sets by call, each two slice buffers the ring steps alternate between (step t
-    // sums in place in the one that step t-1 received into, while the other receives)
-    // (an AdaGrad slice: `pieces` messages of [data rows][delta rows][marks][record], chain_msg)
+    // chained path (chain_push), allocated on its first call: two buffer sets by call,
+    // each two slice buffers the ring steps alternate between (step t sums in place in
+    // the one that step t-1 received into, while the other receives); what a slice
+    // buffer holds depends on the kind (ChainKind, chain_sub)
     void* cbuf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     std::vector<hipEvent_t> cev[2];  // per set: [step][sub-chunk] piece done, then [step][sub-chunk] received
     void* cmd = nullptr;             // AdaGrad: the running step's pending maxDelta candidate (a MaxDelta)
@@ -356,6 +353,320 @@ static bool push_ptrs_aligned(const void* const* bufs, int n) {
     for (int i = 0; i < n; ++i)
         if ((uintptr_t)bufs[i] & 3u) return false;
     return true;
+}
+
+// ---- the chained reduce-scatter: one ring, three kinds of slice -------------------------------
+//
+// Order-exact chained reduce-scatter (contract: include/distml_ps.h). At ring step t rank r
+// holds slice q = (r - t) mod N (the rows of shard q): it adds its pushes' rows of q (a chain
+// piece on cstream; step 0 starts from its own shard, later steps sum in place in what arrived
+// from r-1), then sends q to r+1 and receives slice q-1 from r-1 (one ncclSend + ncclRecv group
+// per sub-chunk on rstream). A slice goes in `pieces` sub-chunks. What step N-1 receives is the
+// rank's own slice after every rank's adds: the store commits it on its stream.
+// The whole call is enqueued with one host wait, the first piece's for the key index; only then
+// is the previous chained call's handle ended (its index errors; its pieces have run by then, or
+// are waited for), so the host runs one call ahead of the ring.
+// A local failure (first = a code) changes no send and no receive: the rank forwards every slice
+// as it holds it.
+enum ChainKind {
+    // fp32 / fp64 rows. A slice buffer holds the slice's rows; sub-chunk k's transfer runs under
+    // sub-chunk k+1's piece (dml_prereduce_chain_piece).
+    kChainPlain,
+    // AdaGrad (dml_prereduce_chain_piece_ada): a slice buffer holds `pieces` message slots, one per
+    // sub-chunk (ChainMsg: data, delta, a touched mark per row); the owner computes alpha once at
+    // its commit. The slice's maxDelta record arrives with its last sub-chunk, so the earlier
+    // sub-chunks' pieces collect their candidates in the group's own record (cmd, kMdDefer); they
+    // are copied into the travelling record once it is there, and the last piece applies them
+    // (kMdApply): one strict > per rank against the earlier ranks, whichever piece held the
+    // rank's best candidate.
+    kChainAda,
+    // Dense int32 (IntMatrixStore): a slice buffer holds [record 32 B][rows]; sub-chunk 0's message
+    // starts at the record, so the verdict is on the rank before any piece of the step runs. A
+    // step is P pieces (dml_prereduce_chain_piece_i32, every add checked), then one close over
+    // the whole slice (dml_prereduce_chain_close_i32: rollback past the step's first negative,
+    // verdict); no sub-chunk leaves the rank before that. The first-negative word of a step is the
+    // handle's Ctrl::neg_pos (all ones after dml_prereduce_begin, handed back so by every close).
+    kChainI32,
+};
+
+// An AdaGrad sub-chunk of nr rows as it travels, one contiguous message: [data nr x
+// cols][delta nr x cols][marks nr x uint32], then, 8-byte aligned, the slice's maxDelta
+// record (a whole MaxDelta, DML_MAXDELTA_RECORD_BYTES) on the slice's last sub-chunk.
+struct ChainMsg {
+    size_t delta, marks, rec, wire;  // byte offsets inside the message; bytes sent
+};
+static ChainMsg chain_msg(int64_t nr, size_t rowb, bool with_rec) {
+    ChainMsg m;
+    m.delta = (size_t)nr * rowb;
+    m.marks = 2 * m.delta;
+    m.rec = (m.marks + (size_t)nr * 4 + 7) & ~(size_t)7;
+    m.wire = with_rec ? m.rec + sizeof(MaxDelta) : m.marks + (size_t)nr * 4;
+    return m;
+}
+
+struct ChainLayout {
+    ChainKind kind;
+    int P;         // sub-chunks per slice
+    size_t rowb;   // bytes of one row of values
+    size_t mslot;  // AdaGrad: one message slot, the longest sub-chunk's message (16-byte aligned)
+    size_t bytes;  // one slice buffer
+};
+static ChainLayout chain_layout(ChainKind kind, int64_t step_rows, int P, size_t rowb) {
+    ChainLayout L{kind, P, rowb, 0, (size_t)step_rows * rowb};
+    if (kind == kChainAda) {
+        L.mslot = (chain_msg((step_rows + P - 1) / P, rowb, true).wire + 15) & ~(size_t)15;
+        L.bytes = L.mslot * (size_t)P;
+    }
+    if (kind == kChainI32) L.bytes += sizeof(ChainI32Rec);
+    return L;
+}
+
+// Sub-chunk k of a slice of `rows` rows: rows [r0, r0 + nr) of the slice (the last may be
+// shorter, or empty), where its message and its rows start in a slice buffer, bytes sent.
+struct ChainSub {
+    int64_t r0, nr;
+    size_t msg, data, wire;
+    ChainMsg m;  // AdaGrad: the planes inside the message
+};
+static ChainSub chain_sub(const ChainLayout& L, int64_t rows, int k) {
+    ChainSub s{};
+    const int64_t per = (rows + L.P - 1) / L.P;
+    s.r0 = std::min<int64_t>((int64_t)k * per, rows);
+    s.nr = std::min<int64_t>(per, rows - s.r0);
+    switch (L.kind) {
+        case kChainPlain:
+            s.msg = s.data = (size_t)s.r0 * L.rowb;
+            s.wire = (size_t)s.nr * L.rowb;
+            break;
+        case kChainAda:
+            s.m = chain_msg(s.nr, L.rowb, k == L.P - 1);
+            s.msg = s.data = (size_t)k * L.mslot;
+            s.wire = s.m.wire;
+            break;
+        case kChainI32:  // sub-chunk 0's message starts at the record
+            s.data = sizeof(ChainI32Rec) + (size_t)s.r0 * L.rowb;
+            s.msg = k == 0 ? 0 : s.data;
+            s.wire = (size_t)s.nr * L.rowb + (k == 0 ? sizeof(ChainI32Rec) : 0);
+            break;
+    }
+    return s;
+}
+// AdaGrad: the slice's maxDelta record sits in its last sub-chunk's slot
+static size_t chain_ada_rec(const ChainLayout& L, int64_t rows) {
+    const ChainSub s = chain_sub(L, rows, L.P - 1);
+    return s.msg + s.m.rec;
+}
+
+static int chain_push(dml_group* g, ChainKind kind, const char* refusal, const void* const* dev_bufs,
+                      const int64_t* lens, int32_t n) {
+    if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
+        return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
+    // the same answer on every rank, before any send: nobody waits for a peer
+    if (refusal) return set_error(DML_E_UNSUPPORTED, refusal);
+    const bool ada = kind == kChainAda, i32 = kind == kChainI32;
+    GHIP(hipSetDevice(g->device));
+    int held = DML_OK;
+    if (g->xheld) {  // an exchange call's slices come first: the store applies calls in order
+        GHIP(hipStreamSynchronize(g->rstream));
+        held = hand_over(g);
+    }
+    // Deliberately not alike: fp / AdaGrad return a failed hand-over at once; an int32 store that is
+    // closed refuses the slices, which must not keep its rank off the ring: reported as `prior` after it.
+    if (!i32) GRC(held);
+    const int W = g->world, P = g->pieces;
+    if (W == 1) {  // one owner: the store's own ordered (int32: checked) push is the chain
+        GRC(held);
+        GRC(end_pending(g, 0));
+        return dml_store_push_batch_device(g->store, dev_bufs, lens, n);
+    }
+    // earlier full-range calls: their applies go onto the store's stream now; what they
+    // report is returned after this call's ring (the rank never leaves the ring)
+    int prior = end_pending(g, 0);
+    if (prior == DML_OK) prior = held;
+    const int64_t C = g->cols;
+    const size_t rowb = (size_t)C * g->vbytes;
+    constexpr size_t kRec = sizeof(ChainI32Rec);
+    constexpr size_t kRecHead = offsetof(MaxDelta, pend);  // value, row, col
+    std::vector<int64_t> f((size_t)W), l((size_t)W);
+    GRC(dml_linear_split(0, g->total_rows - 1, W, f.data(), l.data()));
+    auto srows = [&](int q) { return l[(size_t)q] - f[(size_t)q] + 1; };
+    const ChainLayout L = chain_layout(kind, g->step_rows, P, rowb);
+    if (!g->cbuf[0][0]) {  // first chained call: a group that never makes one pays nothing
+        for (int i = 0; i < 2; ++i) {
+            for (int j = 0; j < 2; ++j) GHIP(hipMalloc(&g->cbuf[i][j], L.bytes));
+            g->cev[i].resize((size_t)2 * W * P, nullptr);
+            for (hipEvent_t& e : g->cev[i]) GHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        GHIP(hipEventCreateWithFlags(&g->cready, hipEventDisableTiming));
+        if (ada) GHIP(hipMalloc(&g->cmd, sizeof(MaxDelta)));
+    }
+    const int set = g->ck;
+    g->ck ^= 1;
+    int first = DML_OK;  // the rank's first local failure of this call
+    auto note = [&](int rc) {
+        if (rc != DML_OK && first == DML_OK) first = rc;
+    };
+    auto hip = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess) note(set_error(DML_E_HIP, std::string(what) + ": " + hipGetErrorString(e)));
+    };
+    // the key index of the rank's pushes over the whole model, on the side stream (it
+    // overlaps the previous call's tail); a push that is not whole records fails here
+    dml_prereduce* h = nullptr;
+    note(dml_prereduce_begin(&g->desc, 0, g->total_rows, g->cols, dev_bufs, lens, n, g->istream, &h));
+    // the shard as every earlier call leaves it: earlier pushes are retired (the store's
+    // value pointer is then current) and cstream waits for what the store's stream holds
+    uint64_t seq = 0;
+    void* shard = nullptr;
+    float* sdelta = nullptr;
+    void* srec = nullptr;  // the store's own record: AdaGrad its running maxDelta, int32 its verdict record
+    int closed = DML_OK;   // int32 only
+    int rs = dml_store_push_seq(g->store, &seq);
+    if (rs == DML_OK) rs = dml_store_retire(g->store, seq);
+    if (i32) {
+        // A store the host knows to be closed (its error state: a negative counter of an earlier
+        // push, or a verdict already collected; one that has just come home is looked at without
+        // waiting) is no failure of this call: the rank's pushes still go to the other shards; its
+        // own slice travels closed.
+        if (rs == DML_OK) closed = store_chain_i32_collect(g->store, false);
+        if (rs == DML_E_NEGATIVE_COUNTER) {
+            closed = rs;
+            rs = DML_OK;
+        }
+        if (closed != DML_OK && closed != DML_E_NEGATIVE_COUNTER) {  // any other store failure: the call's own
+            rs = closed;
+            closed = DML_OK;
+        }
+    }
+    note(rs);
+    GRC(dml_store_device_ptr(g->store, &shard));
+    if (ada) GRC(store_adagrad_ptrs(g->store, &sdelta, &srec));
+    if (i32) GRC(store_chain_i32_record(g->store, &srec));
+    hip(hipEventRecord(g->cready, g->sstream), "hipEventRecord");
+    hip(hipStreamWaitEvent(g->cstream, g->cready, 0), "hipStreamWaitEvent");
+    uint8_t* const B[2] = {(uint8_t*)g->cbuf[set][0], (uint8_t*)g->cbuf[set][1]};
+    hipEvent_t* const pdone = g->cev[set].data();
+    hipEvent_t* const rdone = pdone + (size_t)W * P;
+    const int nxt = (g->rank + 1) % W, prv = (g->rank + W - 1) % W;
+    int crc = DML_OK;  // the transfers' own status
+    // step 0's travelling record of the rank's own slice
+    if (ada) {  // the store's running maxDelta, with no pending candidate
+        uint8_t* const rec = B[0] + chain_ada_rec(L, srows(g->rank));
+        hip(hipMemcpyAsync(rec, srec, kRecHead, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+        hip(hipMemsetAsync(rec + kRecHead, 0, sizeof(MaxDelta) - kRecHead, g->cstream), "hipMemsetAsync");
+    }
+    if (i32) {
+        // the store's device-resident one (a shard an earlier call closed takes no add although
+        // the host has not seen that verdict yet), or closed outright
+        if (closed != DML_OK) hip(hipMemsetAsync(B[0], 0, kRec, g->cstream), "hipMemsetAsync");
+        else hip(hipMemcpyAsync(B[0], srec, kRec, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+    }
+    for (int t = 0; t < W; ++t) {
+        const int q = (g->rank - t + W) % W, qin = (q + W - 1) % W;
+        const int64_t qrows = srows(q);
+        uint8_t* const cur = B[t & 1];       // step t's slice (t > 0: arrived here in step t - 1)
+        uint8_t* const in = B[(t + 1) & 1];  // slice qin lands here
+        uint8_t* const rec = ada ? cur + chain_ada_rec(L, qrows) : cur;  // the slice's record (plain: none)
+        if (ada && P > 1 && first == DML_OK)  // this step's candidates start from none
+            hip(hipMemsetAsync(g->cmd, 0, sizeof(MaxDelta), g->cstream), "hipMemsetAsync");
+        for (int k = 0; k < P; ++k) {
+            const ChainSub s = chain_sub(L, qrows, k);
+            const int64_t r0 = s.r0, nr = s.nr;
+            const bool lastk = k == P - 1;
+            uint8_t* const out = cur + s.data;
+            // an empty sub-chunk is still the step's business where the slice's record travels on
+            // it (AdaGrad: the last, int32: the first)
+            const bool work = nr > 0 || (ada && lastk) || (i32 && k == 0);
+            if (work) {
+                const uint8_t* const base = t == 0 ? (const uint8_t*)shard + (size_t)r0 * rowb : out;
+                if (t > 0) hip(hipStreamWaitEvent(g->cstream, rdone[(t - 1) * P + k], 0), "hipStreamWaitEvent");
+                switch (kind) {
+                    case kChainPlain:
+                        if (first == DML_OK)
+                            note(dml_prereduce_chain_piece(h, nr, nr, f[(size_t)q] + r0, nr, base, out, g->cstream));
+                        // a failed rank forwards the slice as it holds it (step 0: its own shard's rows)
+                        if (first != DML_OK && t == 0)
+                            hip(hipMemcpyAsync(out, base, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+                        break;
+                    case kChainAda: {
+                        const uint8_t* const bdl = t == 0 ? (const uint8_t*)sdelta + (size_t)r0 * rowb : out + s.m.delta;
+                        if (first == DML_OK && lastk && P > 1)
+                            hip(hipMemcpyAsync(rec + kRecHead, (const uint8_t*)g->cmd + kRecHead, sizeof(MaxDelta) - kRecHead,
+                                               hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+                        // a piece over zero rows (the record's) still names a row block of one
+                        if (first == DML_OK)
+                            note(dml_prereduce_chain_piece_ada(h, std::max<int64_t>(nr, 1), std::max<int64_t>(nr, 1),
+                                                               f[(size_t)q] + r0, nr, base, bdl,
+                                                               t == 0 ? nullptr : out + s.m.marks, out, out + s.m.delta,
+                                                               out + s.m.marks, lastk ? (void*)rec : g->cmd, lastk ? 1 : 0, g->cstream));
+                        // a failed rank forwards the slice as it holds it (step 0: its own shard's planes,
+                        // clear marks, the store's record, which is in place already)
+                        if (first != DML_OK && t == 0 && nr > 0) {
+                            hip(hipMemcpyAsync(out, base, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+                            hip(hipMemcpyAsync(out + s.m.delta, bdl, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream),
+                                "hipMemcpyAsync");
+                            hip(hipMemsetAsync(out + s.m.marks, 0, (size_t)nr * 4, g->cstream), "hipMemsetAsync");
+                        }
+                        break;
+                    }
+                    case kChainI32:
+                        if (nr <= 0) break;  // only the record: nothing to add
+                        if (first == DML_OK)
+                            note(dml_prereduce_chain_piece_i32(h, nr, nr, f[(size_t)q] + r0, nr, base, out, cur, g->cstream));
+                        // a failed rank forwards the slice as it holds it (step 0: its own shard's rows, the seeded record)
+                        if (first != DML_OK && t == 0)
+                            hip(hipMemcpyAsync(out, base, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
+                        break;
+                }
+            }
+            // Send timing, deliberate. fp / AdaGrad: sub-chunk k goes right behind piece k, under piece
+            // k+1 (the overlap `pieces` exists for). int32: nothing leaves the rank before the step's
+            // close has the slice's verdict: one event pdone[t] behind the close, then all P sub-chunks.
+            if (i32 && !lastk) continue;
+            if (i32 && first == DML_OK)
+                note(dml_prereduce_chain_close_i32(h, qrows, qrows, f[(size_t)q], qrows, cur + kRec, cur, t, g->cstream));
+            const hipEvent_t ready = i32 ? pdone[t] : work ? pdone[t * P + k] : nullptr;
+            if (ready) {
+                hip(hipEventRecord(ready, g->cstream), "hipEventRecord");
+                hip(hipStreamWaitEvent(g->rstream, ready, 0), "hipStreamWaitEvent");
+            }
+            for (int j = i32 ? 0 : k; j <= k; ++j) {
+                // every rank issues this group, empty sub-chunks included (zero bytes)
+                const ChainSub so = chain_sub(L, qrows, j), si = chain_sub(L, srows(qin), j);
+                ncclResult_t r = ncclGroupStart();
+                if (r == ncclSuccess) r = ncclSend(cur + so.msg, so.wire, ncclUint8, nxt, g->comm, g->rstream);
+                if (r == ncclSuccess) r = ncclRecv(in + si.msg, si.wire, ncclUint8, prv, g->comm, g->rstream);
+                const ncclResult_t re = ncclGroupEnd();
+                if (r == ncclSuccess) r = re;
+                if (r != ncclSuccess && crc == DML_OK)
+                    crc = set_error(DML_E_HIP, std::string("chained ncclSend/ncclRecv: ") + ncclGetErrorString(r));
+                hip(hipEventRecord(rdone[t * P + j], g->rstream), "hipEventRecord");
+            }
+        }
+    }
+    // home: step N-1 received the rank's own slice (and its record), every rank's adds in it
+    hip(hipStreamWaitEvent(g->sstream, rdone[(W - 1) * P + P - 1], 0), "hipStreamWaitEvent");
+    const uint8_t* const home = B[W & 1];
+    int commit = crc;  // failed transfers: nothing to commit
+    if (commit == DML_OK && kind == kChainPlain)
+        commit = dml_store_assign_dense_device(g->store, home, g->shard_rows * C);
+    for (int k = 0; k < P && commit == DML_OK && ada; ++k) {
+        const ChainSub s = chain_sub(L, srows(g->rank), k);
+        const uint8_t* const msg = home + s.msg;
+        if (s.nr > 0 || k == P - 1)
+            commit = store_assign_adagrad(g->store, s.r0, s.nr, msg, msg + s.m.delta, msg + s.m.marks,
+                                          k == P - 1 ? msg + s.m.rec : nullptr);
+    }
+    // int32: a store known closed commits nothing (the slice came home as it left); a verdict is on
+    // its way to the host only after a successful commit
+    if (commit == DML_OK && i32 && closed == DML_OK) {
+        commit = dml_store_assign_dense_i32_device(g->store, home + kRec, g->shard_rows * C, home);
+        if (commit == DML_OK) g->cverdict = true;
+    }
+    if (h) g->cpending.push_back(h);
+    const int older = end_chained(g, 1);  // the previous chained call's key / repeated-row errors
+    // `closed` last (int32; DML_OK otherwise): it is the store's state, not a failure of this call
+    return prior != DML_OK ? prior : first != DML_OK ? first : commit != DML_OK ? commit : older != DML_OK ? older : closed;
 }
 
 extern "C" {
@@ -650,355 +961,26 @@ int dml_group_push_local(dml_group* g, const void* const* dev_bufs, const int64_
     return dml_store_push_batch_device(g->store, dev_bufs, lens, n);
 }
 
-// An AdaGrad sub-chunk of nr rows as it travels, one contiguous message: [data nr x
-// cols][delta nr x cols][marks nr x uint32], then, 8-byte aligned, the slice's maxDelta
-// record (a whole MaxDelta, DML_MAXDELTA_RECORD_BYTES) on the slice's last sub-chunk.
-struct ChainMsg {
-    size_t delta, marks, rec, wire;  // byte offsets inside the message; bytes sent
-};
-static ChainMsg chain_msg(int64_t nr, size_t rowb, bool with_rec) {
-    ChainMsg m;
-    m.delta = (size_t)nr * rowb;
-    m.marks = 2 * m.delta;
-    m.rec = (m.marks + (size_t)nr * 4 + 7) & ~(size_t)7;
-    m.wire = with_rec ? m.rec + sizeof(MaxDelta) : m.marks + (size_t)nr * 4;
-    return m;
-}
-
-// Order-exact chained reduce-scatter (contract: include/distml_ps.h). At ring step t
-// rank r holds slice q = (r - t) mod N (the rows of shard q): it adds its pushes' rows
-// of q (a chain piece on cstream; step 0 starts from its own shard, later steps sum in
-// place in what arrived from r-1), then sends q to r+1 and receives slice q-1 from r-1
-// (one ncclSend + ncclRecv group on rstream). A slice goes in `pieces` sub-chunks:
-// sub-chunk k's transfer runs under sub-chunk k+1's piece. What step N-1 receives is
-// the rank's own slice after every rank's adds: the store commits it on its stream.
-// The whole call is enqueued with one host wait, the first piece's for the key index;
-// only then is the previous chained call's handle ended (its index errors; its pieces
-// have run by then, or are waited for), so the host runs one call ahead of the ring.
-// A local failure (first = a code) changes no send and no receive: the rank forwards
-// every slice as it holds it.
-// AdaGrad groups run the same ring with dml_prereduce_chain_piece_ada. The slice's
-// record arrives with its last sub-chunk, so the earlier sub-chunks' pieces collect
-// their maxDelta candidates in the group's own record (cmd, kMdDefer); they are copied
-// into the travelling record once it is there, and the last piece applies them
-// (kMdApply): one strict > per rank against the earlier ranks, whichever piece held
-// the rank's best candidate.
+// The chained reduce-scatter's two entry points (contract: include/distml_ps.h): which kind of
+// slice the group's matrix travels as, or the refusal; the ring itself is chain_push.
 int dml_group_push_chained(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
-    if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
-        return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
-    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
-    // the same answer on every rank, before any send: nobody waits for a peer
-    const bool ada = g->desc.data_type == DML_DATA_TYPE_MATRIX && g->desc.ada_grad &&
+    const bool ada = g && g->desc.data_type == DML_DATA_TYPE_MATRIX && g->desc.ada_grad &&
                      g->desc.value_type == DML_ELEMENT_TYPE_FLOAT;
-    if ((!g->plain && !ada) || g->desc.value_type == DML_ELEMENT_TYPE_INT)
-        return set_error(DML_E_UNSUPPORTED,
-                         "the chained path serves fp32 / fp64 matrices, plain or AdaGrad (int32: use dml_group_push_exchange)");
-    GHIP(hipSetDevice(g->device));
-    if (g->xheld) {  // an exchange call's slices come first: the store applies calls in order
-        GHIP(hipStreamSynchronize(g->rstream));
-        GRC(hand_over(g));
-    }
-    const int W = g->world, P = g->pieces;
-    if (W == 1) {  // one owner: the store's own ordered push is the chain
-        GRC(end_pending(g, 0));
-        return dml_store_push_batch_device(g->store, dev_bufs, lens, n);
-    }
-    // earlier full-range calls: their applies go onto the store's stream now; what they
-    // report is returned after this call's ring (the rank never leaves the ring)
-    const int prior = end_pending(g, 0);
-    const int64_t C = g->cols;
-    const size_t rowb = (size_t)C * g->vbytes;
-    std::vector<int64_t> f((size_t)W), l((size_t)W);
-    GRC(dml_linear_split(0, g->total_rows - 1, W, f.data(), l.data()));
-    // an AdaGrad slice buffer: `pieces` message slots of the longest sub-chunk's size
-    const int64_t per_max = (g->step_rows + P - 1) / P;
-    const size_t mslot = ada ? (chain_msg(per_max, rowb, true).wire + 15) & ~(size_t)15 : 0;
-    if (!g->cbuf[0][0]) {  // first chained call: a group that never makes one pays nothing
-        const size_t bytes = ada ? mslot * (size_t)P : (size_t)g->step_rows * rowb;
-        for (int i = 0; i < 2; ++i) {
-            for (int j = 0; j < 2; ++j) GHIP(hipMalloc(&g->cbuf[i][j], bytes));
-            g->cev[i].resize((size_t)2 * W * P, nullptr);
-            for (hipEvent_t& e : g->cev[i]) GHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        GHIP(hipEventCreateWithFlags(&g->cready, hipEventDisableTiming));
-        if (ada) GHIP(hipMalloc(&g->cmd, sizeof(MaxDelta)));
-    }
-    const int set = g->ck;
-    g->ck ^= 1;
-    int first = DML_OK;  // the rank's first local failure of this call
-    auto note = [&](int rc) {
-        if (rc != DML_OK && first == DML_OK) first = rc;
-    };
-    auto hip = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess) note(set_error(DML_E_HIP, std::string(what) + ": " + hipGetErrorString(e)));
-    };
-    // the key index of the rank's pushes over the whole model, on the side stream (it
-    // overlaps the previous call's tail); a push that is not whole records fails here
-    dml_prereduce* h = nullptr;
-    note(dml_prereduce_begin(&g->desc, 0, g->total_rows, g->cols, dev_bufs, lens, n, g->istream, &h));
-    // the shard as every earlier call leaves it: earlier pushes are retired (the store's
-    // value pointer is then current) and cstream waits for what the store's stream holds
-    uint64_t seq = 0;
-    void* shard = nullptr;
-    float* sdelta = nullptr;
-    void* smd = nullptr;
-    int rs = dml_store_push_seq(g->store, &seq);
-    if (rs == DML_OK) rs = dml_store_retire(g->store, seq);
-    note(rs);
-    GRC(dml_store_device_ptr(g->store, &shard));
-    if (ada) GRC(store_adagrad_ptrs(g->store, &sdelta, &smd));
-    hip(hipEventRecord(g->cready, g->sstream), "hipEventRecord");
-    hip(hipStreamWaitEvent(g->cstream, g->cready, 0), "hipStreamWaitEvent");
-    uint8_t* const B[2] = {(uint8_t*)g->cbuf[set][0], (uint8_t*)g->cbuf[set][1]};
-    hipEvent_t* const pdone = g->cev[set].data();
-    hipEvent_t* const rdone = pdone + (size_t)W * P;
-    const int nxt = (g->rank + 1) % W, prv = (g->rank + W - 1) % W;
-    int crc = DML_OK;  // the transfers' own status
-    // sub-chunk k of slice q: rows [r0, r0 + nr) of the slice (the last may be shorter, or empty)
-    auto sub = [&](int q, int k, int64_t* r0, int64_t* nr) {
-        const int64_t rows = l[(size_t)q] - f[(size_t)q] + 1, per = (rows + P - 1) / P;
-        *r0 = std::min<int64_t>((int64_t)k * per, rows);
-        *nr = std::min<int64_t>(per, rows - *r0);
-    };
-    constexpr size_t kRecHead = offsetof(MaxDelta, pend);  // value, row, col
-    if (ada) {
-        // the travelling record of the rank's own slice starts as the store's running
-        // maxDelta, with no pending candidate
-        int64_t r0, nr;
-        sub(g->rank, P - 1, &r0, &nr);
-        uint8_t* const rec = B[0] + (size_t)(P - 1) * mslot + chain_msg(nr, rowb, true).rec;
-        hip(hipMemcpyAsync(rec, smd, kRecHead, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
-        hip(hipMemsetAsync(rec + kRecHead, 0, sizeof(MaxDelta) - kRecHead, g->cstream), "hipMemsetAsync");
-    }
-    for (int t = 0; t < W; ++t) {
-        const int q = (g->rank - t + W) % W, qin = (q + W - 1) % W;
-        uint8_t* const cur = B[t & 1];        // step t's slice (t > 0: arrived here in step t - 1)
-        uint8_t* const in = B[(t + 1) & 1];   // slice qin lands here
-        if (ada && P > 1 && first == DML_OK)  // this step's candidates start from none
-            hip(hipMemsetAsync(g->cmd, 0, sizeof(MaxDelta), g->cstream), "hipMemsetAsync");
-        for (int k = 0; k < P; ++k) {
-            int64_t r0, nr, i0, ni;
-            sub(q, k, &r0, &nr);
-            sub(qin, k, &i0, &ni);
-            const bool lastk = k == P - 1;
-            uint8_t* const out = ada ? cur + (size_t)k * mslot : cur + (size_t)r0 * rowb;
-            uint8_t* const land = ada ? in + (size_t)k * mslot : in + (size_t)i0 * rowb;
-            const ChainMsg mo = chain_msg(nr, rowb, lastk), mi = chain_msg(ni, rowb, lastk);
-            if (nr > 0 || (ada && lastk)) {
-                const uint8_t* const base = t == 0 ? (const uint8_t*)shard + (size_t)r0 * rowb : out;
-                if (t > 0) hip(hipStreamWaitEvent(g->cstream, rdone[(t - 1) * P + k], 0), "hipStreamWaitEvent");
-                if (ada) {
-                    const uint8_t* const bdl = t == 0 ? (const uint8_t*)sdelta + (size_t)r0 * rowb : out + mo.delta;
-                    // the slice's record sits in its last sub-chunk's slot
-                    int64_t lr0, lnr;
-                    sub(q, P - 1, &lr0, &lnr);
-                    uint8_t* const rec = cur + (size_t)(P - 1) * mslot + chain_msg(lnr, rowb, true).rec;
-                    if (first == DML_OK && lastk && P > 1)
-                        hip(hipMemcpyAsync(rec + kRecHead, (const uint8_t*)g->cmd + kRecHead, sizeof(MaxDelta) - kRecHead,
-                                           hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
-                    if (first == DML_OK)
-                        note(dml_prereduce_chain_piece_ada(h, std::max<int64_t>(nr, 1), std::max<int64_t>(nr, 1),
-                                                           f[(size_t)q] + r0, nr, base, bdl,
-                                                           t == 0 ? nullptr : out + mo.marks, out, out + mo.delta,
-                                                           out + mo.marks, lastk ? (void*)rec : g->cmd, lastk ? 1 : 0, g->cstream));
-                    // a failed rank forwards the slice as it holds it (step 0: its own shard's planes,
-                    // clear marks, the store's record, which is in place already)
-                    if (first != DML_OK && t == 0 && nr > 0) {
-                        hip(hipMemcpyAsync(out, base, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
-                        hip(hipMemcpyAsync(out + mo.delta, bdl, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream),
-                            "hipMemcpyAsync");
-                        hip(hipMemsetAsync(out + mo.marks, 0, (size_t)nr * 4, g->cstream), "hipMemsetAsync");
-                    }
-                } else {
-                    if (first == DML_OK)
-                        note(dml_prereduce_chain_piece(h, nr, nr, f[(size_t)q] + r0, nr, base, out, g->cstream));
-                    // a failed rank forwards the slice as it holds it (step 0: its own shard's rows)
-                    if (first != DML_OK && t == 0)
-                        hip(hipMemcpyAsync(out, base, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
-                }
-                hip(hipEventRecord(pdone[t * P + k], g->cstream), "hipEventRecord");
-                hip(hipStreamWaitEvent(g->rstream, pdone[t * P + k], 0), "hipStreamWaitEvent");
-            }
-            // every rank issues this group, empty sub-chunks included (zero bytes)
-            const size_t sbytes = ada ? mo.wire : (size_t)nr * rowb, rbytes = ada ? mi.wire : (size_t)ni * rowb;
-            ncclResult_t r = ncclGroupStart();
-            if (r == ncclSuccess) r = ncclSend(out, sbytes, ncclUint8, nxt, g->comm, g->rstream);
-            if (r == ncclSuccess) r = ncclRecv(land, rbytes, ncclUint8, prv, g->comm, g->rstream);
-            const ncclResult_t re = ncclGroupEnd();
-            if (r == ncclSuccess) r = re;
-            if (r != ncclSuccess && crc == DML_OK)
-                crc = set_error(DML_E_HIP, std::string("chained ncclSend/ncclRecv: ") + ncclGetErrorString(r));
-            hip(hipEventRecord(rdone[t * P + k], g->rstream), "hipEventRecord");
-        }
-    }
-    // home: step N-1 received the rank's own slice, every rank's adds in it
-    hip(hipStreamWaitEvent(g->sstream, rdone[(W - 1) * P + P - 1], 0), "hipStreamWaitEvent");
-    int commit = crc;
-    if (commit == DML_OK && !ada) commit = dml_store_assign_dense_device(g->store, B[W & 1], g->shard_rows * C);
-    if (commit == DML_OK && ada) {
-        const uint8_t* const home = B[W & 1];
-        for (int k = 0; k < P && commit == DML_OK; ++k) {
-            int64_t r0, nr;
-            sub(g->rank, k, &r0, &nr);
-            const ChainMsg m = chain_msg(nr, rowb, k == P - 1);
-            const uint8_t* const msg = home + (size_t)k * mslot;
-            if (nr > 0 || k == P - 1)
-                commit = store_assign_adagrad(g->store, r0, nr, msg, msg + m.delta, msg + m.marks,
-                                              k == P - 1 ? msg + m.rec : nullptr);
-        }
-    }
-    if (h) g->cpending.push_back(h);
-    const int older = end_chained(g, 1);  // the previous chained call's key / repeated-row errors
-    return prior != DML_OK ? prior : first != DML_OK ? first : commit != DML_OK ? commit : older;
+    const bool refuse = g && ((!g->plain && !ada) || g->desc.value_type == DML_ELEMENT_TYPE_INT);
+    return chain_push(g, ada ? kChainAda : kChainPlain,
+                      refuse ? "the chained path serves fp32 / fp64 matrices, plain or AdaGrad (int32: use "
+                               "dml_group_push_exchange)"
+                             : nullptr,
+                      dev_bufs, lens, n);
 }
 
-// The chained reduce-scatter of a dense int32 matrix (contract: include/distml_ps.h).
-// The ring, buffers, events and failed-rank rule are dml_group_push_chained's. A slice
-// buffer holds [record 32 B][rows]: sub-chunk 0's message starts at the record, so the
-// verdict is on the rank before any piece of the step runs. Step t on rank r, slice
-// q = (r - t) mod N, all on cstream: P pieces (dml_prereduce_chain_piece_i32, each
-// waiting for its own sub-chunk's receive), then one close over the whole slice
-// (dml_prereduce_chain_close_i32: rollback past the step's first negative, verdict);
-// only then do the step's P send / receive groups follow on rstream. The first-negative
-// word of a step is the handle's Ctrl::neg_pos (all ones after dml_prereduce_begin,
-// handed back so by every close).
 int dml_group_push_chained_i32(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
-    if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
-        return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
-    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
-    // the same answer on every rank, before any send: nobody waits for a peer
-    if (!g->plain || !g->desc.dense_column || g->desc.value_type != DML_ELEMENT_TYPE_INT)
-        return set_error(DML_E_UNSUPPORTED,
-                         "dml_group_push_chained_i32 serves dense int32 matrices (fp32 / fp64, plain or AdaGrad: "
-                         "dml_group_push_chained)");
-    GHIP(hipSetDevice(g->device));
-    int held = DML_OK;  // an exchange call's slices come first; a refusal there does not keep the rank off the ring
-    if (g->xheld) {
-        GHIP(hipStreamSynchronize(g->rstream));
-        held = hand_over(g);
-    }
-    const int W = g->world, P = g->pieces;
-    if (W == 1) {  // one owner: the store's own ordered, checked push is the chain
-        GRC(held);
-        GRC(end_pending(g, 0));
-        return dml_store_push_batch_device(g->store, dev_bufs, lens, n);
-    }
-    int prior = end_pending(g, 0);
-    if (prior == DML_OK) prior = held;
-    const int64_t C = g->cols;
-    const size_t rowb = (size_t)C * g->vbytes;
-    constexpr size_t kRec = sizeof(ChainI32Rec);
-    std::vector<int64_t> f((size_t)W), l((size_t)W);
-    GRC(dml_linear_split(0, g->total_rows - 1, W, f.data(), l.data()));
-    if (!g->cbuf[0][0]) {  // first chained call: a group that never makes one pays nothing
-        for (int i = 0; i < 2; ++i) {
-            for (int j = 0; j < 2; ++j) GHIP(hipMalloc(&g->cbuf[i][j], kRec + (size_t)g->step_rows * rowb));
-            g->cev[i].resize((size_t)2 * W * P, nullptr);
-            for (hipEvent_t& e : g->cev[i]) GHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        GHIP(hipEventCreateWithFlags(&g->cready, hipEventDisableTiming));
-    }
-    const int set = g->ck;
-    g->ck ^= 1;
-    int first = DML_OK;  // the rank's first local failure of this call
-    auto note = [&](int rc) {
-        if (rc != DML_OK && first == DML_OK) first = rc;
-    };
-    auto hip = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess) note(set_error(DML_E_HIP, std::string(what) + ": " + hipGetErrorString(e)));
-    };
-    dml_prereduce* h = nullptr;
-    note(dml_prereduce_begin(&g->desc, 0, g->total_rows, g->cols, dev_bufs, lens, n, g->istream, &h));
-    // The shard as every earlier call leaves it. A store the host knows to be closed (its
-    // error state: a negative counter of an earlier push, or a verdict already collected;
-    // one that has just come home is looked at without waiting) is no failure of this
-    // call: the rank's pushes still go to the other shards; its own slice travels closed.
-    uint64_t seq = 0;
-    void* shard = nullptr;
-    void* srec = nullptr;
-    int closed = DML_OK;
-    int rs = dml_store_push_seq(g->store, &seq);
-    if (rs == DML_OK) rs = dml_store_retire(g->store, seq);
-    if (rs == DML_OK) closed = store_chain_i32_collect(g->store, false);
-    if (rs == DML_E_NEGATIVE_COUNTER) {
-        closed = rs;
-        rs = DML_OK;
-    }
-    if (closed != DML_OK && closed != DML_E_NEGATIVE_COUNTER) {  // any other store failure: the call's own
-        rs = closed;
-        closed = DML_OK;
-    }
-    note(rs);
-    GRC(dml_store_device_ptr(g->store, &shard));
-    GRC(store_chain_i32_record(g->store, &srec));
-    hip(hipEventRecord(g->cready, g->sstream), "hipEventRecord");
-    hip(hipStreamWaitEvent(g->cstream, g->cready, 0), "hipStreamWaitEvent");
-    uint8_t* const B[2] = {(uint8_t*)g->cbuf[set][0], (uint8_t*)g->cbuf[set][1]};
-    hipEvent_t* const pdone = g->cev[set].data();
-    hipEvent_t* const rdone = pdone + (size_t)W * P;
-    const int nxt = (g->rank + 1) % W, prv = (g->rank + W - 1) % W;
-    int crc = DML_OK;  // the transfers' own status
-    auto sub = [&](int q, int k, int64_t* r0, int64_t* nr) {
-        const int64_t rows = l[(size_t)q] - f[(size_t)q] + 1, per = (rows + P - 1) / P;
-        *r0 = std::min<int64_t>((int64_t)k * per, rows);
-        *nr = std::min<int64_t>(per, rows - *r0);
-    };
-    // step 0's record: the store's device-resident one (a shard an earlier call closed takes
-    // no add although the host has not seen that verdict yet), or closed outright
-    if (closed != DML_OK) hip(hipMemsetAsync(B[0], 0, kRec, g->cstream), "hipMemsetAsync");
-    else hip(hipMemcpyAsync(B[0], srec, kRec, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
-    for (int t = 0; t < W; ++t) {
-        const int q = (g->rank - t + W) % W, qin = (q + W - 1) % W;
-        uint8_t* const cur = B[t & 1];       // step t's slice (t > 0: arrived here in step t - 1)
-        uint8_t* const in = B[(t + 1) & 1];  // slice qin lands here
-        const int64_t qrows = l[(size_t)q] - f[(size_t)q] + 1;
-        for (int k = 0; k < P; ++k) {
-            int64_t r0, nr;
-            sub(q, k, &r0, &nr);
-            if (nr <= 0 && k > 0) continue;
-            uint8_t* const out = cur + kRec + (size_t)r0 * rowb;
-            const uint8_t* const base = t == 0 ? (const uint8_t*)shard + (size_t)r0 * rowb : out;
-            if (t > 0) hip(hipStreamWaitEvent(g->cstream, rdone[(t - 1) * P + k], 0), "hipStreamWaitEvent");
-            if (nr <= 0) continue;
-            if (first == DML_OK) note(dml_prereduce_chain_piece_i32(h, nr, nr, f[(size_t)q] + r0, nr, base, out, cur, g->cstream));
-            // a failed rank forwards the slice as it holds it (step 0: its own shard's rows, the seeded record)
-            if (first != DML_OK && t == 0)
-                hip(hipMemcpyAsync(out, base, (size_t)nr * rowb, hipMemcpyDeviceToDevice, g->cstream), "hipMemcpyAsync");
-        }
-        // the slice's verdict, before any of it leaves the rank
-        if (first == DML_OK)
-            note(dml_prereduce_chain_close_i32(h, qrows, qrows, f[(size_t)q], qrows, cur + kRec, cur, t, g->cstream));
-        hip(hipEventRecord(pdone[t], g->cstream), "hipEventRecord");
-        hip(hipStreamWaitEvent(g->rstream, pdone[t], 0), "hipStreamWaitEvent");
-        for (int k = 0; k < P; ++k) {
-            int64_t r0, nr, i0, ni;
-            sub(q, k, &r0, &nr);
-            sub(qin, k, &i0, &ni);
-            // sub-chunk 0's message starts at the record; every rank issues every group (empty ones: zero bytes)
-            const uint8_t* const src = k == 0 ? cur : cur + kRec + (size_t)r0 * rowb;
-            uint8_t* const land = k == 0 ? in : in + kRec + (size_t)i0 * rowb;
-            const size_t sbytes = (size_t)nr * rowb + (k == 0 ? kRec : 0), rbytes = (size_t)ni * rowb + (k == 0 ? kRec : 0);
-            ncclResult_t r = ncclGroupStart();
-            if (r == ncclSuccess) r = ncclSend(src, sbytes, ncclUint8, nxt, g->comm, g->rstream);
-            if (r == ncclSuccess) r = ncclRecv(land, rbytes, ncclUint8, prv, g->comm, g->rstream);
-            const ncclResult_t re = ncclGroupEnd();
-            if (r == ncclSuccess) r = re;
-            if (r != ncclSuccess && crc == DML_OK)
-                crc = set_error(DML_E_HIP, std::string("chained ncclSend/ncclRecv: ") + ncclGetErrorString(r));
-            hip(hipEventRecord(rdone[t * P + k], g->rstream), "hipEventRecord");
-        }
-    }
-    // home: step N-1 received the rank's own slice and its record. A store known closed
-    // commits nothing (the slice came home as it left).
-    hip(hipStreamWaitEvent(g->sstream, rdone[(W - 1) * P + P - 1], 0), "hipStreamWaitEvent");
-    int commit = crc;
-    if (commit == DML_OK && closed == DML_OK) {
-        commit = dml_store_assign_dense_i32_device(g->store, B[W & 1] + kRec, g->shard_rows * C, B[W & 1]);
-        if (commit == DML_OK) g->cverdict = true;
-    }
-    if (h) g->cpending.push_back(h);
-    const int older = end_chained(g, 1);  // the previous chained call's key / repeated-row errors
-    return prior != DML_OK ? prior : first != DML_OK ? first : commit != DML_OK ? commit : older != DML_OK ? older : closed;
+    const bool refuse = g && (!g->plain || !g->desc.dense_column || g->desc.value_type != DML_ELEMENT_TYPE_INT);
+    return chain_push(g, kChainI32,
+                      refuse ? "dml_group_push_chained_i32 serves dense int32 matrices (fp32 / fp64, plain or AdaGrad: "
+                               "dml_group_push_chained)"
+                             : nullptr,
+                      dev_bufs, lens, n);
 }
 
 int dml_group_debug_fail_verify(dml_group* g, int32_t nth) {

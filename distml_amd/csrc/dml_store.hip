@@ -2132,6 +2132,54 @@ static void prereduce_free(dml_prereduce* p) {
     delete p;
 }
 
+// ---- what a piece, the int32 close and a failed speculation's re-run share on the host ----
+static RowMap piece_row_map(const dml_prereduce* p, int64_t block, int64_t stride, int64_t off, void* out) {
+    RowMap rm;
+    rm.block = block;
+    rm.stride = stride;
+    rm.off = off;
+    rm.rows_total = p->rows;
+    rm.out = out;
+    return rm;
+}
+// Pieces on another stream (the index ran on a side stream, overlapping the caller's previous
+// work): wait for the index on the host, then enqueue the piece straight behind whatever that
+// stream runs (no cross-queue barrier). And the handle's completion event, on first use.
+static int piece_begin(dml_prereduce* p, hipStream_t st) {
+    if (st != p->stream && !p->idx_waited) {
+        HIPCHK(hipEventSynchronize(p->idx_ev));
+        p->idx_waited = true;
+    }
+    if (!p->last_ev) HIPCHK(hipEventCreateWithFlags(&p->last_ev, hipEventDisableTiming));
+    return DML_OK;
+}
+// A sampled call's (p->timed) start / stop pair for one launch, from the pool; the handle keeps
+// it until dml_prereduce_end has read it.
+static int piece_timing_pair(dml_prereduce* p, std::pair<hipEvent_t, hipEvent_t>* t) {
+    *t = {nullptr, nullptr};
+    {
+        std::lock_guard<std::mutex> lk(g_pre_mu);
+        if (!g_pre_pool.empty()) {
+            *t = g_pre_pool.back();
+            g_pre_pool.pop_back();
+        }
+    }
+    if (!t->first) {
+        HIPCHK(hipEventCreate(&t->first));
+        HIPCHK(hipEventCreate(&t->second));
+    }
+    p->tev.push_back(*t);
+    return DML_OK;
+}
+// model rows a piece covered: blocks of row_block task rows at row_off + q*row_stride
+static void piece_count_rows(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off, int64_t ntask_rows) {
+    for (int64_t t0 = 0; t0 < ntask_rows; t0 += row_block) {
+        const int64_t lo = (t0 / row_block) * row_stride + row_off;
+        const int64_t hi = std::min(lo + std::min(row_block, ntask_rows - t0), p->rows);
+        if (hi > lo) p->rows_done += hi - lo;
+    }
+}
+
 // Read a context call's verdict once its pieces are done; if speculation failed,
 // re-run the call exactly on the context's stream: a fresh slot table, the full
 // key index (repeated rows detected), every recorded piece without speculation.
@@ -2181,12 +2229,7 @@ static int prereduce_verify(dml_prereduce* p, int32_t* rerun) {
                             kNoPos, xs));
         AdaArgs none{};
         for (const auto& pr : p->prec) {
-            RowMap rm;
-            rm.block = pr.block;
-            rm.stride = pr.stride;
-            rm.off = pr.off;
-            rm.rows_total = p->rows;
-            rm.out = pr.out;
+            const RowMap rm = piece_row_map(p, pr.block, pr.stride, pr.off, pr.out);
             HIPCHK(launch_reduce(p->desc.value_type, kPreReduce, pr.out, pr.ntask, p->cols, bt, p->nb, p->stride,
                                  p->K, W.slot, nullptr, W.ctrl, kNoPos, none, xs, nullptr, LaunchEv{}, rm));
         }
@@ -2303,25 +2346,12 @@ int dml_prereduce_moments_piece(dml_prereduce* p, int64_t row_block, int64_t row
     if (p->ctx || p->desc.value_type != DML_ELEMENT_TYPE_FLOAT || p->cols % 4 || p->cols * 4 >= 4096)
         return set_err(DML_E_UNSUPPORTED, "two-moment pieces: f32 rows of whole 16-B vectors under 4 KiB");
     hipStream_t st = (hipStream_t)stream;
-    if (st != p->stream && !p->idx_waited) {
-        HIPCHK(hipEventSynchronize(p->idx_ev));
-        p->idx_waited = true;
-    }
-    RowMap rm;
-    rm.block = row_block;
-    rm.stride = row_stride;
-    rm.off = row_off;
-    rm.rows_total = p->rows;
-    rm.out = dev_out;
-    if (!p->last_ev) HIPCHK(hipEventCreateWithFlags(&p->last_ev, hipEventDisableTiming));
+    if (int rc = piece_begin(p, st)) return rc;
+    const RowMap rm = piece_row_map(p, row_block, row_stride, row_off, dev_out);
     HIPCHK(launch_moments(ntask_rows, p->cols, p->bt, p->nb, p->stride, p->K, p->slot, p->ctrl, rm, st,
                           LaunchEv{nullptr, p->last_ev}));
     p->done_ev = p->last_ev;
-    for (int64_t t0 = 0; t0 < ntask_rows; t0 += row_block) {
-        const int64_t lo = (t0 / row_block) * row_stride + row_off;
-        const int64_t hi = std::min(lo + std::min(row_block, ntask_rows - t0), p->rows);
-        if (hi > lo) p->rows_done += hi - lo;
-    }
+    piece_count_rows(p, row_block, row_stride, row_off, ntask_rows);
     p->last_st = st;
     return DML_OK;
 }
@@ -2363,41 +2393,18 @@ static int prereduce_piece(dml_prereduce* p, int mode, int64_t row_block, int64_
         }
         if (p->bt.ident_ok) p->hidx = p->hctrl;  // the verdict k_flat_ident is chosen from
     }
-    if (st != p->stream && !p->idx_waited) {
-        // pieces on another stream (the index ran on a side stream, overlapping the
-        // caller's previous work): wait for the index on the host, then enqueue the
-        // piece straight behind whatever that stream runs (no cross-queue barrier)
-        HIPCHK(hipEventSynchronize(p->idx_ev));
-        p->idx_waited = true;
-    }
-    RowMap rm;
-    rm.block = row_block;
-    rm.stride = row_stride;
-    rm.off = row_off;
-    rm.rows_total = p->rows;
-    rm.out = dev_out;
+    if (int rc = piece_begin(p, st)) return rc;
+    RowMap rm = piece_row_map(p, row_block, row_stride, row_off, dev_out);
     rm.base = dev_base;
     rm.rec = dev_record;
     if (mode == kChainCheckI32) p->slots_kept = true;
     AdaArgs none{};
-    if (!p->last_ev) HIPCHK(hipEventCreateWithFlags(&p->last_ev, hipEventDisableTiming));
     // the piece's completion event rides in its dispatch packet (no marker packet between pieces)
     LaunchEv ev{nullptr, p->last_ev};
     if (ap) ev.stop = nullptr;  // the candidates' finalize follows the kernel: last_ev is recorded behind it
-    if (p->timed) {
-        std::pair<hipEvent_t, hipEvent_t> t{nullptr, nullptr};
-        {
-            std::lock_guard<std::mutex> lk(g_pre_mu);
-            if (!g_pre_pool.empty()) {
-                t = g_pre_pool.back();
-                g_pre_pool.pop_back();
-            }
-        }
-        if (!t.first) {
-            HIPCHK(hipEventCreate(&t.first));
-            HIPCHK(hipEventCreate(&t.second));
-        }
-        p->tev.push_back(t);
+    if (p->timed) {  // both timing events ride in the packet too
+        std::pair<hipEvent_t, hipEvent_t> t;
+        if (int rc = piece_timing_pair(p, &t)) return rc;
         ev = LaunchEv{t.first, t.second};
     }
     // all-identity calls (seen in the index's Ctrl, once the host has waited for it):
@@ -2436,12 +2443,7 @@ static int prereduce_piece(dml_prereduce* p, int mode, int64_t row_block, int64_
                              p->K, p->slot, nullptr, p->ctrl, kNoPos, none, st, nullptr, ev, rm));
     p->done_ev = ev.stop;
     if (mode == kPreReduce) p->prec.push_back({row_block, row_stride, row_off, ntask_rows, dev_out});
-    // model rows this piece covered: blocks of row_block task rows at row_off + q*row_stride
-    for (int64_t t0 = 0; t0 < ntask_rows; t0 += row_block) {
-        const int64_t lo = (t0 / row_block) * row_stride + row_off;
-        const int64_t hi = std::min(lo + std::min(row_block, ntask_rows - t0), p->rows);
-        if (hi > lo) p->rows_done += hi - lo;
-    }
+    piece_count_rows(p, row_block, row_stride, row_off, ntask_rows);
     p->last_st = st;
     return DML_OK;
 }
@@ -2513,32 +2515,14 @@ int dml_prereduce_chain_close_i32(dml_prereduce* p, int64_t row_block, int64_t r
         return set_err(DML_E_INVALID_ARG, "bad int32 chain close arguments");
     if (int rc = chain_i32_refusal(p)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (st != p->stream && !p->idx_waited) {
-        HIPCHK(hipEventSynchronize(p->idx_ev));
-        p->idx_waited = true;
-    }
-    RowMap rm;
-    rm.block = row_block;
-    rm.stride = row_stride;
-    rm.off = row_off;
-    rm.rows_total = p->rows;
-    rm.out = dev_slice;
-    if (!p->last_ev) HIPCHK(hipEventCreateWithFlags(&p->last_ev, hipEventDisableTiming));
+    if (int rc = piece_begin(p, st)) return rc;
+    const RowMap rm = piece_row_map(p, row_block, row_stride, row_off, dev_slice);
     LaunchEv ev{nullptr, p->last_ev};
     if (p->timed) {
-        std::pair<hipEvent_t, hipEvent_t> t{nullptr, nullptr};
-        {
-            std::lock_guard<std::mutex> lk(g_pre_mu);
-            if (!g_pre_pool.empty()) {
-                t = g_pre_pool.back();
-                g_pre_pool.pop_back();
-            }
-        }
-        if (!t.first) {
-            HIPCHK(hipEventCreate(&t.first));
-            HIPCHK(hipEventCreate(&t.second));
-        }
-        p->tev.push_back(t);
+        // two launches under one pair: the start event is recorded ahead of the rollback, not
+        // put into a packet as the pieces do; the stop event rides in the verdict's
+        std::pair<hipEvent_t, hipEvent_t> t;
+        if (int rc = piece_timing_pair(p, &t)) return rc;
         HIPCHK(hipEventRecord(t.first, st));
         ev.stop = t.second;
     }

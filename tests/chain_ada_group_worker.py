@@ -1,7 +1,7 @@
 """One rank of the native shard group's chained reduce-scatter on an AdaGrad
 matrix (dml_group_push_chained, FloatMatrixStoreAdaGrad descriptor) in a torch-free
 process; tests/test_native_chain_ada.py starts `world` of these over the RCCL
-stand-in (--double, see tests/native_group_worker.py) or the system RCCL.
+stand-in (--double, see tests/group_ranks.py) or the system RCCL.
 
 Cases (inputs from tests/chain_ada_expect.py, shared with the test's oracle):
   chain   three chained calls back to back, no flush between; call 1: rank 0 passes
@@ -15,43 +15,17 @@ Cases (inputs from tests/chain_ada_expect.py, shared with the test's oracle):
           maxDelta through nativeMaxDelta
 Writes out/<case>_<rank>.npz (data, delta, alpha as bytes, md) and prints one JSON line.
 """
-import argparse
-import ctypes as C
-import json
-import os
-import sys
+import numpy as np
 
-sys.modules["torch"] = None  # any `import torch` now raises ImportError
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
-
-import numpy as np  # noqa: E402
-
-from native_group_worker import DOUBLE, Hip, read_uid  # noqa: E402
+import group_ranks as R
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--world", type=int, required=True)
-    ap.add_argument("--rank", type=int, required=True)
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--uid-file", required=True)
-    ap.add_argument("--case", required=True)
-    ap.add_argument("--rows", type=int, default=1000)
-    ap.add_argument("--cols", type=int, default=64)
-    ap.add_argument("--pieces", type=int, default=1)
-    ap.add_argument("--asc", type=int, default=0)
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--double", action="store_true")
-    a = ap.parse_args()
-    dbl = C.CDLL(DOUBLE, mode=C.RTLD_GLOBAL) if a.double else None  # before libdistml_ps.so
-    from distml_amd import DataDesc, _lib
+    a, H, uid = R.start()
+    from distml_amd import DataDesc
     from distml_amd.group import NativeShardGroup
     import chain_ada_expect as A
     import chain_expect as X
-    _lib.load()
-    H = Hip(a.device)
-    uid = read_uid(a.uid_file, a.rank)
     world, rank, rows, cols = a.world, a.rank, a.rows, a.cols
     errors, res = [], {}
     first, last = X.shard_ranges(world, rows)[rank]
@@ -135,14 +109,7 @@ def main():
         jvm.call("nativeGroupDestroy", gh)
     else:
         raise SystemExit(f"unknown case {a.case}")
-    H.free()
-    np.savez(os.path.join(a.out, f"{a.case}_{rank}.npz"), **res)
-    calls_n = None
-    if dbl is not None:
-        dbl.rccl_double_calls.restype = C.c_int64
-        calls_n = int(dbl.rccl_double_calls())
-    libs = {n: ln.split()[-1] for ln in open("/proc/self/maps") for n in ("librccl", "libdistml_ps") if n in ln}
-    print(json.dumps({"rank": rank, "errors": errors, "double_calls": calls_n, "libs": libs}), flush=True)
+    R.finish(a, H, errors, res)
 
 
 if __name__ == "__main__":

@@ -2,10 +2,7 @@
 what the JNI's GpuShardGroup binds) in a process that never imports torch, as the
 PS JVM runs it. tests/test_native_group.py starts `world` of these.
 
---double: dlopen tests/rccl_double/librccl_double.so with RTLD_GLOBAL before
-libdistml_ps.so, so the library's nccl* calls resolve to the test-only stand-in
-(ranks sharing one GPU over host shared memory; RCCL refuses two ranks per
-device). Without it the ranks use the system RCCL, one GPU each.
+Options, the stand-in (--double) and the closing JSON line: tests/group_ranks.py.
 
 Cases (generators shared with tests/test_gpu_group.py):
   full      CALLS full-range calls back to back (call 2: rank 0's push 0 fails the
@@ -26,86 +23,17 @@ Cases (generators shared with tests/test_gpu_group.py):
             entry points (integration/jni/dml_jni.cc on the mock JNIEnv of tests/jni_mock)
 Writes out/<case>_<rank>.npz and prints one JSON line.
 """
-import argparse
-import ctypes as C
-import json
-import os
-import sys
-import time
+import numpy as np
 
-sys.modules["torch"] = None  # any `import torch` now raises ImportError
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
-DOUBLE = os.path.join(ROOT, "tests", "rccl_double", "librccl_double.so")
-
-import numpy as np  # noqa: E402
-
-
-class Hip:
-    """hipMalloc / hipMemcpy of the HIP runtime libdistml_ps.so loaded."""
-
-    def __init__(self, device):
-        path = [ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln][0]
-        h = C.CDLL(path)
-        h.hipSetDevice.argtypes = [C.c_int]
-        h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        h.hipFree.argtypes = [C.c_void_p]
-        assert h.hipSetDevice(device) == 0
-        self.h, self.ptrs = h, []
-
-    def put(self, arr: np.ndarray) -> int:
-        arr = np.ascontiguousarray(arr)
-        p = C.c_void_p()
-        assert self.h.hipMalloc(C.byref(p), max(arr.nbytes, 1)) == 0
-        assert self.h.hipMemcpy(p, arr.ctypes.data, arr.nbytes, 1) == 0  # host to device
-        self.ptrs.append(p.value)
-        return p.value
-
-    def free(self):
-        for p in self.ptrs:
-            self.h.hipFree(C.c_void_p(p))
-        self.ptrs = []
-
-
-def read_uid(path, rank, timeout=120.0):
-    from distml_amd.group import NativeShardGroup
-    if rank == 0 and not os.path.exists(path):
-        tmp = path + ".tmp"
-        with open(tmp, "wb") as f:
-            f.write(NativeShardGroup.unique_id())
-        os.replace(tmp, path)
-    t0 = time.time()
-    while not os.path.exists(path):
-        if time.time() - t0 > timeout:
-            raise TimeoutError("no unique id from rank 0")
-        time.sleep(0.05)
-    return open(path, "rb").read()
+import group_ranks as R
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--world", type=int, required=True)
-    ap.add_argument("--rank", type=int, required=True)
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--uid-file", required=True)
-    ap.add_argument("--case", required=True)
-    ap.add_argument("--vt", type=int, default=1)
-    ap.add_argument("--rows", type=int, default=1000)
-    ap.add_argument("--cols", type=int, default=64)
-    ap.add_argument("--pushes", type=int, default=5)
-    ap.add_argument("--pieces", type=int, default=1)
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--double", action="store_true")
-    a = ap.parse_args()
-    dbl = C.CDLL(DOUBLE, mode=C.RTLD_GLOBAL) if a.double else None  # before libdistml_ps.so
-    from distml_amd import DataDesc, _lib
+    a, H, uid = R.start(pushes=5)
+    from distml_amd import DataDesc
     from distml_amd.group import NativeShardGroup
     import pyoracle
     import test_gpu_group as G
-    _lib.load()
-    H = Hip(a.device)
-    uid = read_uid(a.uid_file, a.rank)
     world, rank = a.world, a.rank
     errors, res = [], {}
     if a.case in ("full", "fault", "local", "beginfail", "asc"):
@@ -201,17 +129,7 @@ def main():
         raise SystemExit(f"unknown case {a.case}")
     if g is not None:
         g.close()
-    H.free()
-    np.savez(os.path.join(a.out, f"{a.case}_{rank}.npz"), **res)
-    calls, ctas = None, None
-    if dbl is not None:
-        dbl.rccl_double_calls.restype = C.c_int64
-        calls = int(dbl.rccl_double_calls())
-        dbl.rccl_double_ctas.restype = C.c_int32
-        ctas = [int(dbl.rccl_double_ctas(0)), int(dbl.rccl_double_ctas(1))]
-    libs = {n: ln.split()[-1] for ln in open("/proc/self/maps") for n in ("librccl", "libdistml_ps")
-            if n in ln}
-    print(json.dumps({"rank": rank, "errors": errors, "double_calls": calls, "ctas": ctas, "libs": libs}), flush=True)
+    R.finish(a, H, errors, res)
 
 
 if __name__ == "__main__":

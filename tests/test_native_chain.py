@@ -11,52 +11,19 @@ other bytes on these inputs, so a chain in the wrong order cannot pass.
 test_native_chain_rccl_all_devices runs the same over the system RCCL where the
 box has more than one GPU (skipped on one).
 """
-import json
-import os
-import subprocess
-import sys
+import functools
 
 import numpy as np
 import pytest
 
 import chain_expect as X
+import group_ranks as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WORKER = os.path.join(ROOT, "tests", "chain_group_worker.py")
 pytestmark = pytest.mark.gpu
-DELAY_US = 20000
 CALLS = 3
 
 
-def run_ranks(tmp_path, world, case, double=True, **kw):
-    uid = tmp_path / f"uid_{case}"
-    if double:  # the stand-in's id names its shared-memory segment (tests/test_native_group.py)
-        name = ("dml-rccl-double:/dmlrccl_" + os.urandom(12).hex()).encode()
-        uid.write_bytes(name + b"\0" * (128 - len(name)))
-    args = [f"--{k.replace('_', '-')}={v}" for k, v in kw.items()]
-    env = dict(os.environ, DML_RCCL_DOUBLE_DELAY_US=str(DELAY_US))
-    procs = []
-    for r in range(world):
-        cmd = [sys.executable, "-u", WORKER, f"--world={world}", f"--rank={r}", f"--uid-file={uid}",
-               f"--case={case}", f"--out={tmp_path}", f"--device={0 if double else r}"] + args
-        procs.append(subprocess.Popen(cmd + (["--double"] if double else []), stdout=subprocess.PIPE,
-                                      stderr=subprocess.PIPE, text=True, env=env))
-    outs = []
-    try:
-        for p in procs:
-            o, e = p.communicate(timeout=240)
-            assert p.returncode == 0, f"rank {procs.index(p)} rc {p.returncode}:\n{e[-3000:]}"
-            outs.append(json.loads([ln for ln in o.splitlines() if ln.startswith("{")][-1]))
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait()
-    for d in outs:
-        assert "libdistml_ps" in d["libs"], d
-        if double and world > 1 and case != "unsup":
-            assert d["double_calls"] > 0, d  # the transfers ran through the stand-in
-    return outs
+run_ranks = functools.partial(R.run_ranks, "chain_group_worker.py", no_transfers=("unsup",))
 
 
 def shard_bytes(tmp_path, case, r, vt, cols):
@@ -70,9 +37,11 @@ def assert_shards(tmp_path, case, world, vt, cols, want):
 
 
 # 1000 rows: shards of 334, 334, 332 rows at world 3 (pieces 4: sub-chunks of 84, 84, 84, 82 /
-# 83 x 4), 250 at world 4; 1198 x 200 ascending: the up-front identity check and k_flat_ident
+# 83 x 4), 250 at world 4; 1198 x 200 ascending: the up-front identity check and k_flat_ident;
+# 100 rows, pieces 8: shards of 34, 34, 32, sub-chunks of 5 x 6, 4, 0 / 4 x 8 — an empty last
+# sub-chunk is sent while a non-empty one is received, and the reverse
 CHAIN_CASES = [(1, 1, 1000, 64, 1, 0), (2, 1, 1000, 64, 1, 0), (3, 1, 1000, 64, 2, 0), (4, 1, 1000, 67, 1, 0),
-               (3, 1, 1000, 64, 4, 0), (3, 3, 1000, 64, 2, 0), (3, 1, 1198, 200, 1, 1)]
+               (3, 1, 1000, 64, 4, 0), (3, 3, 1000, 64, 2, 0), (3, 1, 1198, 200, 1, 1), (3, 1, 100, 64, 8, 0)]
 
 
 def run_chain_case(tmp_path, oracle, world, vt, rows, cols, pieces, asc, double=True):

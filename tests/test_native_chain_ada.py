@@ -13,53 +13,19 @@ rank-major on these generators' inputs.
 test_native_chain_ada_rccl_all_devices runs the same over the system RCCL where the
 box has more than one GPU (skipped on one).
 """
-import json
-import os
-import subprocess
-import sys
+import functools
 
 import numpy as np
 import pytest
 
 import chain_ada_expect as A
 import chain_expect as X
+import group_ranks as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WORKER = os.path.join(ROOT, "tests", "chain_ada_group_worker.py")
 pytestmark = pytest.mark.gpu
-DELAY_US = 20000
 
 
-def run_ranks(tmp_path, world, case, double=True, **kw):
-    """test_native_chain.run_ranks with this file's worker."""
-    uid = tmp_path / f"uid_{case}"
-    if double:  # the stand-in's id names its shared-memory segment (tests/test_native_group.py)
-        name = ("dml-rccl-double:/dmlrccl_" + os.urandom(12).hex()).encode()
-        uid.write_bytes(name + b"\0" * (128 - len(name)))
-    args = [f"--{k.replace('_', '-')}={v}" for k, v in kw.items()]
-    env = dict(os.environ, DML_RCCL_DOUBLE_DELAY_US=str(DELAY_US))
-    procs = []
-    for r in range(world):
-        cmd = [sys.executable, "-u", WORKER, f"--world={world}", f"--rank={r}", f"--uid-file={uid}",
-               f"--case={case}", f"--out={tmp_path}", f"--device={0 if double else r}"] + args
-        procs.append(subprocess.Popen(cmd + (["--double"] if double else []), stdout=subprocess.PIPE,
-                                      stderr=subprocess.PIPE, text=True, env=env))
-    outs = []
-    try:
-        for p in procs:
-            o, e = p.communicate(timeout=240)
-            assert p.returncode == 0, f"rank {procs.index(p)} rc {p.returncode}:\n{e[-3000:]}"
-            outs.append(json.loads([ln for ln in o.splitlines() if ln.startswith("{")][-1]))
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait()
-    for d in outs:
-        assert "libdistml_ps" in d["libs"], d
-        if double and world > 1:
-            assert d["double_calls"] > 0, d  # the transfers ran through the stand-in
-    return outs
+run_ranks = functools.partial(R.run_ranks, "chain_ada_group_worker.py")
 
 
 def assert_ranks(tmp_path, case, world, cols, want):
@@ -75,9 +41,11 @@ def assert_ranks(tmp_path, case, world, cols, want):
 
 # 1198 x 200 ascending: the vector stream; 1000 x 64 permuted: the slot-table shape. 1000 rows:
 # shards of 334, 334, 332 at world 3 (a short last shard; pieces 3: sub-chunks of 112, 112, 110 /
-# 111, 111, 110), 250 at world 4; 1198 rows: 400, 400, 398 at world 3
+# 111, 111, 110), 250 at world 4; 1198 rows: 400, 400, 398 at world 3; 100 rows, pieces 8: shards
+# of 34, 34, 32, sub-chunks of 5 x 6, 4, 0 / 4 x 8 — the 34-row slices' maxDelta record travels on
+# an empty last sub-chunk, sent while a non-empty one is received, and the reverse
 CHAIN_CASES = [(1, 1000, 64, 1, 0), (2, 1198, 200, 3, 1), (3, 1000, 64, 3, 0), (3, 1198, 200, 1, 1),
-               (4, 1000, 64, 1, 0), (4, 1198, 200, 3, 1)]
+               (4, 1000, 64, 1, 0), (4, 1198, 200, 3, 1), (3, 100, 64, 8, 0), (3, 100, 200, 8, 1)]
 
 
 def run_chain_case(tmp_path, oracle, world, rows, cols, pieces, asc, double=True):

@@ -10,54 +10,20 @@ int32 oracle store per shard, fed the ring order and stopped at its first negati
 test_native_chain_i32_rccl_all_devices runs the clean case over the system RCCL where
 the box has more than one GPU (skipped on one).
 """
-import json
-import os
-import subprocess
-import sys
+import functools
 
 import numpy as np
 import pytest
 
 import chain_expect as X
 import chain_i32_expect as E
+import group_ranks as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WORKER = os.path.join(ROOT, "tests", "chain_i32_group_worker.py")
 pytestmark = pytest.mark.gpu
-DELAY_US = 20000
 ISE, AIOOBE = "IllegalStateException", "ArrayIndexOutOfBoundsException"
 
 
-def run_ranks(tmp_path, world, case, double=True, **kw):
-    """test_native_chain.run_ranks with this file's worker."""
-    uid = tmp_path / f"uid_{case}"
-    if double:  # the stand-in's id names its shared-memory segment (tests/test_native_group.py)
-        name = ("dml-rccl-double:/dmlrccl_" + os.urandom(12).hex()).encode()
-        uid.write_bytes(name + b"\0" * (128 - len(name)))
-    args = [f"--{k.replace('_', '-')}={v}" for k, v in kw.items()]
-    env = dict(os.environ, DML_RCCL_DOUBLE_DELAY_US=str(DELAY_US))
-    procs = []
-    for r in range(world):
-        cmd = [sys.executable, "-u", WORKER, f"--world={world}", f"--rank={r}", f"--uid-file={uid}",
-               f"--case={case}", f"--out={tmp_path}", f"--device={0 if double else r}"] + args
-        procs.append(subprocess.Popen(cmd + (["--double"] if double else []), stdout=subprocess.PIPE,
-                                      stderr=subprocess.PIPE, text=True, env=env))
-    outs = []
-    try:
-        for p in procs:
-            o, e = p.communicate(timeout=240)
-            assert p.returncode == 0, f"rank {procs.index(p)} rc {p.returncode}:\n{e[-3000:]}"
-            outs.append(json.loads([ln for ln in o.splitlines() if ln.startswith("{")][-1]))
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait()
-    for d in outs:
-        assert "libdistml_ps" in d["libs"], d
-        if double and world > 1 and case != "refuse":
-            assert d["double_calls"] > 0, d  # the transfers ran through the stand-in
-    return outs
+run_ranks = functools.partial(R.run_ranks, "chain_i32_group_worker.py", no_transfers=("refuse",))
 
 
 def assert_ranks(tmp_path, case, world, cols, want):
@@ -81,12 +47,15 @@ def assert_only_owner_reports(outs, owner, want, first_where=None):
 
 
 # 1000 rows: shards of 500 at world 2; 334, 334, 332 at world 3 (pieces 2: sub-chunks of 167 / 166);
-# 250 at world 4. 67 columns: pair-packed k_reduce_rows; 256: FULL; 3: k_reduce
-CHAIN_CASES = [(2, 67, 1), (3, 67, 2), (4, 256, 2), (3, 3, 1)]
+# 250 at world 4. 67 columns: pair-packed k_reduce_rows; 256: FULL; 3: k_reduce. 100 rows, pieces 8:
+# shards of 34, 34, 32 in sub-chunks of 5 x 6, 4, 0 / 4 x 8 — a step skips the piece of an empty
+# sub-chunk, and an empty last sub-chunk is sent while a non-empty one is received, and the reverse
+# (the adds commute and init >= 1000 keeps every count positive: this pins the plumbing, not the order)
+CHAIN_CASES = [(2, 67, 1, 1000), (3, 67, 2, 1000), (4, 256, 2, 1000), (3, 3, 1, 1000), (3, 67, 8, 100)]
+CHAIN_IDS = ["-".join(map(str, c if c[3] != 1000 else c[:3])) for c in CHAIN_CASES]
 
 
-def run_chain_case(tmp_path, oracle, world, cols, pieces, double=True):
-    rows = 1000
+def run_chain_case(tmp_path, oracle, world, cols, pieces, double=True, rows=1000):
     outs = run_ranks(tmp_path, world, "chain", double=double, rows=rows, cols=cols, pieces=pieces)
     assert all(not d["errors"] for d in outs), outs
     want = E.expected(oracle, world, rows, cols, E.group_calls(world, rows, cols, "chain"), E.init_counts(rows, cols))
@@ -94,11 +63,11 @@ def run_chain_case(tmp_path, oracle, world, cols, pieces, double=True):
     assert_ranks(tmp_path, "chain", world, cols, want)
 
 
-@pytest.mark.parametrize("world,cols,pieces", CHAIN_CASES)
-def test_native_chain_i32(tmp_path, oracle, world, cols, pieces):
+@pytest.mark.parametrize("world,cols,pieces,rows", CHAIN_CASES, ids=CHAIN_IDS)
+def test_native_chain_i32(tmp_path, oracle, world, cols, pieces, rows):
     """Three clean chained calls back to back without a flush (the two buffer sets rotate),
     W = 3; in call 1 rank 0 passes no push. Byte-equal, no error anywhere."""
-    run_chain_case(tmp_path, oracle, world, cols, pieces)
+    run_chain_case(tmp_path, oracle, world, cols, pieces, rows=rows)
 
 
 @pytest.mark.parametrize("world,cols,pieces", [(2, 67, 2), (3, 1000, 2), (4, 67, 1)])

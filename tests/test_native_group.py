@@ -16,61 +16,20 @@ Checks as tests/test_gpu_group.py: fp32 within the reduce-scatter bound of
 DESIGN.md §2 (check_full_range), int32 and the exchange path bit-exact, the
 two-moment path within 1e-6 (kat.moments_within).
 """
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+import group_ranks as R
 import kat
 import test_gpu_group as G
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WORKER = os.path.join(ROOT, "tests", "native_group_worker.py")
-DOUBLE = os.path.join(ROOT, "tests", "rccl_double", "librccl_double.so")
 pytestmark = pytest.mark.gpu
 
-
-# Every collective of the stand-in runs this long after its inputs are ready (helper
-# thread, asynchronous to the caller's streams): a stream dependency the library
-# forgets shows up as wrong sums (VERDICT r4 #2).
-DELAY_US = 20000
-
-
-def run_ranks(tmp_path, world, case, double=True, delay_us=DELAY_US, **kw):
-    """Start `world` workers, wait for all, return their JSON lines (rank order)."""
-    uid = tmp_path / f"uid_{case}"
-    if double:
-        # the stand-in's id names its shared-memory segment (rccl_double.cc's format);
-        # written here without loading the stand-in, whose HIP runtime (/opt/rocm) must
-        # not join torch's in this process
-        name = ("dml-rccl-double:/dmlrccl_" + os.urandom(12).hex()).encode()
-        uid.write_bytes(name + b"\0" * (128 - len(name)))
-    args = [f"--{k.replace('_', '-')}={v}" for k, v in kw.items()]
-    env = dict(os.environ, DML_RCCL_DOUBLE_DELAY_US=str(delay_us))
-    procs = []
-    for r in range(world):
-        cmd = [sys.executable, "-u", WORKER, f"--world={world}", f"--rank={r}", f"--uid-file={uid}",
-               f"--case={case}", f"--out={tmp_path}", f"--device={0 if double else r}"] + args
-        procs.append(subprocess.Popen(cmd + (["--double"] if double else []), stdout=subprocess.PIPE,
-                                      stderr=subprocess.PIPE, text=True, env=env))
-    outs = []
-    try:
-        for p in procs:
-            o, e = p.communicate(timeout=240)
-            assert p.returncode == 0, f"rank {procs.index(p)} rc {p.returncode}:\n{e[-3000:]}"
-            outs.append(json.loads([ln for ln in o.splitlines() if ln.startswith("{")][-1]))
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait()
+def run_ranks(tmp_path, world, case, double=True, **kw):
+    """group_ranks.run_ranks with this file's worker; over the stand-in, the channel count too."""
+    outs = R.run_ranks("native_group_worker.py", tmp_path, world, case, double=double, **kw)
     for d in outs:
-        assert "libdistml_ps" in d["libs"], d
         if double:
-            assert d["double_calls"] > 0, d  # the collectives ran through the stand-in
             # the communicator pins RCCL's channel count (ncclCommInitRankConfig, DESIGN.md §6)
             assert d["ctas"] == [128, 128], d
     return outs
