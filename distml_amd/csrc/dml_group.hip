@@ -35,16 +35,10 @@
 #include <string>
 #include <vector>
 
-#include "distml_ps.h"
-#include "dml_internal.h"
+#include "dml_host.h"
 
 using namespace dml;
 
-#define GHIP(x)                                                                                        \
-    do {                                                                                               \
-        hipError_t e_ = (x);                                                                           \
-        if (e_ != hipSuccess) return set_error(DML_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 #define GNCCL(x)                                                                                       \
     do {                                                                                               \
         ncclResult_t r_ = (x);                                                                         \
@@ -268,14 +262,14 @@ void group_free(dml_group* g) {
 }
 
 int group_init(dml_group* g, const uint8_t* unique_id) {
-    GHIP(hipSetDevice(g->device));
+    HIPCHK(hipSetDevice(g->device));
     int lo = 0, hi = 0;
-    GHIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    GHIP(hipStreamCreateWithFlags(&g->cstream, hipStreamNonBlocking));
-    GHIP(hipStreamCreateWithPriority(&g->istream, hipStreamNonBlocking, hi));
+    HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    HIPCHK(hipStreamCreateWithFlags(&g->cstream, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithPriority(&g->istream, hipStreamNonBlocking, hi));
     // RCCL's stream is high-priority too: a reduce-scatter's blocks are dispatched
     // ahead of the next call's pre-reduce blocks when both wait for CUs
-    GHIP(hipStreamCreateWithPriority(&g->rstream, hipStreamNonBlocking, hi));
+    HIPCHK(hipStreamCreateWithPriority(&g->rstream, hipStreamNonBlocking, hi));
     // linearSplit(world): every rank's slice of the partial is step_rows long
     std::vector<int64_t> f((size_t)g->world), l((size_t)g->world);
     GRC(dml_linear_split(0, g->total_rows - 1, g->world, f.data(), l.data()));
@@ -288,12 +282,12 @@ int group_init(dml_group* g, const uint8_t* unique_id) {
     GRC(dml_store_stream(g->store, &ss));
     g->sstream = (hipStream_t)ss;
     for (int i = 0; i < 2; ++i) {
-        GHIP(hipEventCreateWithFlags(&g->rs_done[i], hipEventDisableTiming));
-        GHIP(hipEventCreateWithFlags(&g->applied[i], hipEventDisableTiming));
-        GHIP(hipEventCreateWithFlags(&g->xsent[i], hipEventDisableTiming));
-        GHIP(hipEventCreateWithFlags(&g->xconsumed[i], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&g->rs_done[i], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&g->applied[i], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&g->xsent[i], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&g->xconsumed[i], hipEventDisableTiming));
     }
-    GHIP(hipMalloc((void**)&g->xcnt, sizeof(int64_t) * 4 * (size_t)g->world * kMaxW));
+    HIPCHK(hipMalloc((void**)&g->xcnt, sizeof(int64_t) * 4 * (size_t)g->world * kMaxW));
     ncclUniqueId id;
     memcpy(&id, unique_id, sizeof id);
     // The reduce-scatter's channel count is pinned instead of left to RCCL's tuning: one
@@ -313,8 +307,8 @@ int ensure_partials(dml_group* g) {
     const size_t part = (size_t)g->world * (size_t)g->step_rows * (size_t)g->cols * g->vbytes;
     const size_t rcv = (size_t)g->step_rows * (size_t)g->cols * g->vbytes;
     for (int i = 0; i < 2; ++i) {
-        GHIP(hipMalloc(&g->partial[i], part));
-        if (g->world > 1) GHIP(hipMalloc(&g->recv[i], rcv));  // one rank applies the partial itself
+        HIPCHK(hipMalloc(&g->partial[i], part));
+        if (g->world > 1) HIPCHK(hipMalloc(&g->recv[i], rcv));  // one rank applies the partial itself
     }
     GRC(dml_prectx_create(&g->desc, 0, g->total_rows, g->cols, g->device, &g->pctx));
     return DML_OK;
@@ -329,31 +323,23 @@ int hand_over(dml_group* g) {
     const int rc = dml_store_push_batch_device(g->store, g->xptrs.data(), g->xlens.data(), (int32_t)g->xptrs.size());
     // the store's device reads of the set are queued on its stream by now (index
     // host-waited, reduce enqueued); its host-side retire may read them once more
-    GHIP(hipEventRecord(g->xconsumed[g->xheld_set], g->sstream));
+    HIPCHK(hipEventRecord(g->xconsumed[g->xheld_set], g->sstream));
     GRC(dml_store_push_seq(g->store, &g->xseq[g->xheld_set]));
     return rc;
 }
 
 int grow(void** p, int64_t* cap, int64_t need) {
     if (*cap >= need) return DML_OK;
-    if (*p) GHIP(hipFree(*p));
+    if (*p) HIPCHK(hipFree(*p));
     *p = nullptr;
     *cap = 0;
     const int64_t n = std::max<int64_t>(need, 1) + (need >> 3);  // 12.5 % headroom for the next call
-    GHIP(hipMalloc(p, (size_t)n));
+    HIPCHK(hipMalloc(p, (size_t)n));
     *cap = n;
     return DML_OK;
 }
 
 }  // namespace
-
-// Device push pointers are 4-byte aligned (include/distml_ps.h). An argument error like a
-// null pointer: refused before the group's state moves or the rank joins a collective.
-static bool push_ptrs_aligned(const void* const* bufs, int n) {
-    for (int i = 0; i < n; ++i)
-        if ((uintptr_t)bufs[i] & 3u) return false;
-    return true;
-}
 
 // ---- the chained reduce-scatter: one ring, three kinds of slice -------------------------------
 //
@@ -461,14 +447,14 @@ static int chain_push(dml_group* g, ChainKind kind, const char* refusal, const v
                       const int64_t* lens, int32_t n) {
     if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
         return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
-    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, kMisalignedPush);
     // the same answer on every rank, before any send: nobody waits for a peer
     if (refusal) return set_error(DML_E_UNSUPPORTED, refusal);
     const bool ada = kind == kChainAda, i32 = kind == kChainI32;
-    GHIP(hipSetDevice(g->device));
+    HIPCHK(hipSetDevice(g->device));
     int held = DML_OK;
     if (g->xheld) {  // an exchange call's slices come first: the store applies calls in order
-        GHIP(hipStreamSynchronize(g->rstream));
+        HIPCHK(hipStreamSynchronize(g->rstream));
         held = hand_over(g);
     }
     // Deliberately not alike: fp / AdaGrad return a failed hand-over at once; an int32 store that is
@@ -494,12 +480,12 @@ static int chain_push(dml_group* g, ChainKind kind, const char* refusal, const v
     const ChainLayout L = chain_layout(kind, g->step_rows, P, rowb);
     if (!g->cbuf[0][0]) {  // first chained call: a group that never makes one pays nothing
         for (int i = 0; i < 2; ++i) {
-            for (int j = 0; j < 2; ++j) GHIP(hipMalloc(&g->cbuf[i][j], L.bytes));
+            for (int j = 0; j < 2; ++j) HIPCHK(hipMalloc(&g->cbuf[i][j], L.bytes));
             g->cev[i].resize((size_t)2 * W * P, nullptr);
-            for (hipEvent_t& e : g->cev[i]) GHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            for (hipEvent_t& e : g->cev[i]) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
-        GHIP(hipEventCreateWithFlags(&g->cready, hipEventDisableTiming));
-        if (ada) GHIP(hipMalloc(&g->cmd, sizeof(MaxDelta)));
+        HIPCHK(hipEventCreateWithFlags(&g->cready, hipEventDisableTiming));
+        if (ada) HIPCHK(hipMalloc(&g->cmd, sizeof(MaxDelta)));
     }
     const int set = g->ck;
     g->ck ^= 1;
@@ -729,12 +715,12 @@ int dml_group_store(dml_group* g, dml_store** store) {
 int dml_group_push_full_range(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
     if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
         return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
-    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, kMisalignedPush);
     if (!g->plain)
         return set_error(DML_E_UNSUPPORTED, "the full-range pre-reduce path needs a plain-sum matrix (use dml_group_push_exchange)");
-    GHIP(hipSetDevice(g->device));
+    HIPCHK(hipSetDevice(g->device));
     if (g->xheld) {  // an exchange call's slices come first: the store applies calls in order
-        GHIP(hipStreamSynchronize(g->rstream));
+        HIPCHK(hipStreamSynchronize(g->rstream));
         GRC(hand_over(g));
     }
     GRC(end_chained(g, 0));  // chained calls are committed on the store's stream already: their index errors
@@ -772,8 +758,8 @@ int dml_group_push_full_range(dml_group* g, const void* const* dev_bufs, const i
 int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
     if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
         return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
-    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
-    GHIP(hipSetDevice(g->device));
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, kMisalignedPush);
+    HIPCHK(hipSetDevice(g->device));
     // full-range calls still waiting for their reduce-scatter come first: the store
     // applies calls in order
     GRC(end_pending(g, 0));
@@ -784,7 +770,7 @@ int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int
     const int verdict = chain_i32_verdict(g);
     const int W = g->world;
     if (W == 1 && verdict != DML_OK) return verdict;
-    const int64_t K = g->desc.key_type == 0 ? 4 : 8;
+    const int64_t K = desc_key_bytes(g->desc);
     const int64_t stride = g->desc.data_type == DML_DATA_TYPE_MATRIX ? K + (int64_t)g->vbytes * g->cols
                                                                       : K + (int64_t)g->vbytes;
     if (W == 1 && n > 0) {
@@ -798,7 +784,7 @@ int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int
         for (int b = 0; b < n; ++b) whole = whole && cnt[(size_t)b] * stride == lens[b];
         if (whole) {
             if (g->xheld) {  // the previous exchange call's slices come first
-                GHIP(hipStreamSynchronize(g->rstream));
+                HIPCHK(hipStreamSynchronize(g->rstream));
                 GRC(hand_over(g));
             }
             return dml_store_push_batch_device(g->store, dev_bufs, lens, n);
@@ -813,7 +799,7 @@ int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int
     g->xk ^= 1;
     int64_t total = 0;
     for (int b = 0; b < n; ++b) total += lens[b];
-    GHIP(hipEventSynchronize(g->xsent[i]));  // the set's last all-to-all (two calls ago) read xsend[i]
+    HIPCHK(hipEventSynchronize(g->xsent[i]));  // the set's last all-to-all (two calls ago) read xsend[i]
     std::vector<int64_t> cnt((size_t)n * W, 0);  // [push][dest]
     // a local failure (a push that is not whole records, a HIP error) still takes part
     // in both exchanges, sending nothing, so that no peer waits for this rank; the
@@ -829,15 +815,15 @@ int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int
         for (int b = 0; b < n; ++b) mine[(size_t)d * n + b] = cnt[(size_t)b * W + d];
     int64_t* dmine = g->xcnt + (size_t)i * 2 * W * kMaxW;
     int64_t* dtheirs = dmine + (size_t)W * kMaxW;
-    GHIP(hipMemcpyAsync(dmine, mine.data(), sizeof(int64_t) * mine.size(), hipMemcpyHostToDevice, g->rstream));
+    HIPCHK(hipMemcpyAsync(dmine, mine.data(), sizeof(int64_t) * mine.size(), hipMemcpyHostToDevice, g->rstream));
     GNCCL(ncclGroupStart());
     for (int q = 0; q < W; ++q) {
         GNCCL(ncclSend(dmine + (size_t)q * n, (size_t)n, ncclInt64, q, g->comm, g->rstream));
         GNCCL(ncclRecv(dtheirs + (size_t)q * n, (size_t)n, ncclInt64, q, g->comm, g->rstream));
     }
     GNCCL(ncclGroupEnd());
-    GHIP(hipMemcpyAsync(theirs.data(), dtheirs, sizeof(int64_t) * theirs.size(), hipMemcpyDeviceToHost, g->rstream));
-    GHIP(hipStreamSynchronize(g->rstream));  // also completes the previous call's all-to-all
+    HIPCHK(hipMemcpyAsync(theirs.data(), dtheirs, sizeof(int64_t) * theirs.size(), hipMemcpyDeviceToHost, g->rstream));
+    HIPCHK(hipStreamSynchronize(g->rstream));  // also completes the previous call's all-to-all
     GRC(hand_over(g));
     std::vector<int64_t> soff((size_t)W + 1, 0), roff((size_t)W + 1, 0);
     for (int q = 0; q < W; ++q) {
@@ -853,9 +839,9 @@ int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int
     // (host side) before the buffer is rewritten or freed, its reduce ran before
     // this call's all-to-all writes it (device side)
     GRC(dml_store_retire(g->store, g->xseq[i]));
-    if (g->xrecv_cap[i] < roff[(size_t)W]) GHIP(hipEventSynchronize(g->xconsumed[i]));
+    if (g->xrecv_cap[i] < roff[(size_t)W]) HIPCHK(hipEventSynchronize(g->xconsumed[i]));
     GRC(grow(&g->xrecv[i], &g->xrecv_cap[i], roff[(size_t)W]));
-    GHIP(hipStreamWaitEvent(g->rstream, g->xconsumed[i], 0));
+    HIPCHK(hipStreamWaitEvent(g->rstream, g->xconsumed[i], 0));
     uint8_t* sp = (uint8_t*)g->xsend[i];
     uint8_t* rp = (uint8_t*)g->xrecv[i];
     GNCCL(ncclGroupStart());
@@ -866,7 +852,7 @@ int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int
                        g->rstream));
     }
     GNCCL(ncclGroupEnd());
-    GHIP(hipEventRecord(g->xsent[i], g->rstream));
+    HIPCHK(hipEventRecord(g->xsent[i], g->rstream));
     // the owner's pushes, rank-major: rank 0's pushes in order, then rank 1's, ...
     g->xptrs.clear();
     g->xlens.clear();
@@ -888,22 +874,22 @@ int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int
 int dml_group_push_moments(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
     if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
         return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
-    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, kMisalignedPush);
     if (!g->desc.ada_grad || g->desc.value_type != DML_ELEMENT_TYPE_FLOAT)
         return set_error(DML_E_UNSUPPORTED, "the two-moment path is for AdaGrad (float) matrices");
-    GHIP(hipSetDevice(g->device));
+    HIPCHK(hipSetDevice(g->device));
     if (g->xheld) {  // earlier calls' slices first: the store applies calls in order
-        GHIP(hipStreamSynchronize(g->rstream));
+        HIPCHK(hipStreamSynchronize(g->rstream));
         GRC(hand_over(g));
     }
     GRC(end_pending(g, 0));
     const int64_t S = g->step_rows, W = g->world, C = g->cols;
     if (!g->mpart[0]) {
         for (int i = 0; i < 2; ++i) {
-            GHIP(hipMalloc(&g->mpart[i], (size_t)(W * S * 2 * C) * sizeof(float)));
-            GHIP(hipMalloc(&g->mrecv[i], (size_t)(S * 2 * C) * sizeof(float)));
-            GHIP(hipEventCreateWithFlags(&g->mrs_done[i], hipEventDisableTiming));
-            GHIP(hipEventCreateWithFlags(&g->mapplied[i], hipEventDisableTiming));
+            HIPCHK(hipMalloc(&g->mpart[i], (size_t)(W * S * 2 * C) * sizeof(float)));
+            HIPCHK(hipMalloc(&g->mrecv[i], (size_t)(S * 2 * C) * sizeof(float)));
+            HIPCHK(hipEventCreateWithFlags(&g->mrs_done[i], hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&g->mapplied[i], hipEventDisableTiming));
         }
     }
     const int k = g->mk;
@@ -935,10 +921,10 @@ int dml_group_push_moments(dml_group* g, const void* const* dev_bufs, const int6
         (void)dml_prereduce_end(h);
         return set_error(DML_E_HIP, std::string("ncclReduceScatter: ") + ncclGetErrorString(r));
     }
-    GHIP(hipEventRecord(g->mrs_done[k], g->rstream));
-    GHIP(hipStreamWaitEvent(g->sstream, g->mrs_done[k], 0));
+    HIPCHK(hipEventRecord(g->mrs_done[k], g->rstream));
+    HIPCHK(hipStreamWaitEvent(g->sstream, g->mrs_done[k], 0));
     GRC(dml_store_apply_adagrad_moments_device(g->store, g->mrecv[k], g->shard_rows));
-    GHIP(hipEventRecord(g->mapplied[k], g->sstream));
+    HIPCHK(hipEventRecord(g->mapplied[k], g->sstream));
     g->mpending.push_back(h);
     return end_moments(g, 1);  // the previous call's errors
 }
@@ -949,10 +935,10 @@ int dml_group_push_moments(dml_group* g, const void* const* dev_bufs, const int6
 int dml_group_push_local(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n) {
     if (!g || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
         return set_error(DML_E_INVALID_ARG, "bad push arguments (n must be <= 64)");
-    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, "device push pointer is not 4-byte aligned");
-    GHIP(hipSetDevice(g->device));
+    if (!push_ptrs_aligned(dev_bufs, n)) return set_error(DML_E_INVALID_ARG, kMisalignedPush);
+    HIPCHK(hipSetDevice(g->device));
     if (g->xheld) {  // the last exchange call's slices
-        GHIP(hipStreamSynchronize(g->rstream));
+        HIPCHK(hipStreamSynchronize(g->rstream));
         GRC(hand_over(g));
     }
     GRC(end_pending(g, 0));  // full-range calls waiting for their reduce-scatter and apply
@@ -991,7 +977,7 @@ int dml_group_debug_fail_verify(dml_group* g, int32_t nth) {
 
 int dml_group_flush(dml_group* g) {
     if (!g) return set_error(DML_E_INVALID_ARG, "null group");
-    GHIP(hipSetDevice(g->device));
+    HIPCHK(hipSetDevice(g->device));
     int rc = DML_OK;
     if (g->xheld) {  // the last exchange call's slices
         rc = hipStreamSynchronize(g->rstream) == hipSuccess ? DML_OK : set_error(DML_E_HIP, "exchange sync");

@@ -13,8 +13,12 @@
 // int32 adds past the first negative counter (exact mod 2^32), and turn the
 // first failing position into the status code, key and column the reference's
 // exception carries.
-#include "distml_ps.h"
-#include "dml_internal.h"
+//
+// Also here: the thread-local error string (dml_last_error, dml::set_error), the
+// synthetic-data calls and the dml_diag_* floors. The sharded path's pre-reduce engine
+// (dml_reduce_buckets_dense, dml_prereduce_*, dml_prectx_*) is dml_prereduce.hip; what the
+// host translation units share (HIPCHK, DeviceGuard, the push tallies) is dml_host.h.
+#include "dml_host.h"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -24,7 +28,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
-#include <atomic>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -42,24 +45,6 @@ static int set_err(int code, const std::string& msg) {
     return code;
 }
 int dml::set_error(int code, const std::string& msg) { return set_err(code, msg); }
-
-// Device push pointers are 4-byte aligned (include/distml_ps.h): every kernel reads keys
-// as dwords and values with 4-byte-aligned 16-B loads. The entry points that take device
-// pushes refuse anything else before they launch or change state (dml_shard_split,
-// dml_split.hip, checks the same way).
-static const char* const kMisalignedPush = "device push pointer is not 4-byte aligned";
-static bool push_ptrs_aligned(const void* const* bufs, int n) {
-    for (int i = 0; i < n; ++i)
-        if ((uintptr_t)bufs[i] & 3u) return false;
-    return true;
-}
-
-#define HIPCHK(x)                                                                                  \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) return set_err(DML_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 
 namespace {
 
@@ -156,18 +141,6 @@ void java_unit_abs_gaussian_row(JavaRandom& jr, double* row, int64_t cols) {
 }
 
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 struct Chunk {
     Batch bt{};
     int nb = 0;
@@ -187,11 +160,8 @@ int vtype_of(const dml_desc& d) { return d.value_type; }
 
 }  // namespace
 
-// One workspace of the pipeline: [Ctrl | slot rows x kMaxW | rowflag rows].
-// Ring of kRing, at most kRing-1 chunks pending: chunk j's index reuses chunk
-// j-3's workspace, whose Ctrl chunk j-2 read as `prev` — and chunk j-2 has been
-// retired before chunk j launches.
-constexpr int kRing = 3;
+// One workspace of the pipeline: [Ctrl | slot rows x kMaxW | rowflag rows], in a ring of
+// kRing (dml_host.h).
 struct Workspace {
     uint8_t* base = nullptr;
     Ctrl* ctrl = nullptr;
@@ -227,7 +197,7 @@ struct Pending {
 struct dml_store {
     std::mutex mu;
     int device = 0;
-    int64_t ident_full_min = (int64_t)64 << 20;  // DML_KNOB_IDENT_FULL_MIN_BYTES
+    int64_t ident_full_min = kIdentFullMinBytes;  // DML_KNOB_IDENT_FULL_MIN_BYTES
     hipStream_t stream = nullptr;     // applies (reduce / scatter-add), in push order
     hipStream_t istream = nullptr;    // key index of the next chunk, overlapping the current apply
     hipStream_t cstream = nullptr;    // ctrl read-back, off the apply stream
@@ -547,17 +517,13 @@ int launch_chunk(dml_store* s, Chunk& c, Workspace& W, const Ctrl* prev) {
         // AdaGrad chunks of k_ada_flat (no speculation: the apply cannot be undone):
         // full-range pushes whose records are rows in order skip the key index after a
         // complete key check, when the slot table is beyond the caches (its atomics go
-        // to DRAM; see dml_prereduce_begin)
+        // to DRAM; see prereduce_begin_tail, dml_prereduce.hip)
         c.bt.ident_ok = 0;
         if (s->adagrad && c.tail_cut == kNoPos &&
-            (int64_t)s->rows * slot_stride(c.nb) * 4 > s->ident_full_min &&
-            use_flat(vtype_of(s->desc), reduce_mode(s), s->cols, c.bt, c.nb, s->rows)) {
-            bool full = c.nb > 0;
-            for (int j = 0; j < c.nb && full; ++j) full = c.bt.nrec[j] == s->rows;
-            if (full) {
-                HIPCHK(launch_ident_full(c.bt, c.nb, c.max_nrec, s->stride, s->K, s->first, s->rows, W.ctrl, is));
-                c.bt.ident_ok = 1;
-            }
+            use_flat(vtype_of(s->desc), reduce_mode(s), s->cols, c.bt, c.nb, s->rows) &&
+            full_range_beyond_caches(c.bt, c.nb, s->rows, s->ident_full_min)) {
+            HIPCHK(launch_ident_full(c.bt, c.nb, c.max_nrec, s->stride, s->K, s->first, s->rows, W.ctrl, is));
+            c.bt.ident_ok = 1;
         }
         // Sparse-row chunks of k_reduce_rows (some push lists only part of the rows): the
         // index marks the rows any push lists, and the reduce skips the others' shard rows
@@ -824,16 +790,7 @@ int retire_front(dml_store* s) {
     if (c.spec && ctl.spec_ok != 0u) {
         std::swap(s->data, s->data_alt);  // every identity record verified: the output is the shard
         s->st.spec_chunks += 1;
-        uint64_t perm = 0;
-        for (int b = 0; b < c.nb; ++b) {
-            if (ctrl_identity(&ctl, ctl.ident, b)) {
-                s->st.identity_pushes += 1;
-                continue;
-            }
-            if ((ctl.ident >> b) & 1ull) s->st.reused_pushes += 1;
-            else s->st.indexed_pushes += 1;
-            perm |= 1ull << ctrl_col(&ctl, b);  // a verified permutation (indexed or reused)
-        }
+        const uint64_t perm = tally_verified_pushes(ctl, c.nb, s->st);
         if (c.keeps) {  // the reduce left the slot table as built: the next chunk here may reuse it
             W.clean = false;
             W.kept = true;
@@ -852,10 +809,7 @@ int retire_front(dml_store* s) {
     } else if (s->is_matrix) {
         // non-speculative: AdaGrad chunks may have skipped the index for pushes checked
         // completely (Batch::ident_ok)
-        for (int b = 0; b < c.nb; ++b) {
-            if (c.bt.ident_ok && ((ctl.ident >> b) & 1ull)) s->st.identity_pushes += 1;
-            else s->st.indexed_pushes += 1;
-        }
+        tally_checked_pushes(ctl, c.nb, c.bt.ident_ok != 0, s->st);
     }
     int rc = DML_OK;
     if (s->is_matrix && ctl.no_dup == 0u) {
@@ -970,7 +924,7 @@ int run_batch(dml_store* s, const uint8_t* const* dptr, const int64_t* lens, int
             c.tail_cut = std::min(c.tail_cut, tcut);
         }
         if (c.max_nrec == 0 && c.tail_cut == kNoPos) continue;  // empty pushes: nothing to apply
-        while ((int)s->pend.size() >= kRing - 1) {  // see Workspace
+        while ((int)s->pend.size() >= kRing - 1) {  // see kRing
             int rc = retire_front(s);
             if (rc) { s->pend.clear(); return rc; }
         }
@@ -1173,7 +1127,7 @@ int dml_store_create_range(const dml_desc* desc, int64_t first_key, int64_t last
     s->no_spec = (flags & DML_FLAG_NO_SPECULATION) != 0;
     s->is_matrix = d.data_type == 1;
     s->adagrad = s->is_matrix && d.value_type == DML_ELEMENT_TYPE_FLOAT && d.ada_grad;
-    s->K = d.key_type == 0 ? 4 : 8;
+    s->K = desc_key_bytes(d);
     s->V = (d.value_type == DML_ELEMENT_TYPE_INT || d.value_type == DML_ELEMENT_TYPE_FLOAT) ? 4 : 8;
     s->array_vs = s->V;
     if (!s->is_matrix && d.value_type == DML_ELEMENT_TYPE_FLOAT && (flags & DML_FLAG_FLOAT_ARRAY_REF_STRIDE))
@@ -1893,930 +1847,12 @@ int dml_store_apply_adagrad_moments_device(dml_store* s, const void* dev_src, in
     return DML_OK;
 }
 
-}  // extern "C"
-
-// Per-device pool of pre-reduce workspaces (Ctrl + slot table + rowflags).
-// hipMalloc/hipFree per step cost ~0.2 ms of host time (hipFree synchronizes
-// the device); leases are taken and returned instead, one per in-flight call.
-struct WsLease {
-    uint8_t* ptr = nullptr;
-    size_t bytes = 0;
-    bool clean = false;     // slot table all -1 and rowflags 0 (left so by a clearing pre-reduce)
-    Ctrl* hctrl = nullptr;  // pinned host copy of the Ctrl (read without touching a stream)
-    // the model rows `clean` was established for: a lease serves any model that fits, and
-    // a call of another size lays the table and the rowflags out elsewhere (entries a
-    // larger, failed call left beyond a smaller call's table are still there)
-    int64_t clean_rows = 0;
-};
-static std::mutex g_ws_mu;
-static std::unordered_map<int, std::vector<WsLease>> g_ws_free;
-
-static int ws_acquire(int dev, size_t bytes, WsLease* out) {
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mu);
-        auto& v = g_ws_free[dev];
-        for (size_t i = 0; i < v.size(); ++i)
-            if (v[i].bytes >= bytes) {
-                *out = v[i];
-                v.erase(v.begin() + (ptrdiff_t)i);
-                return DML_OK;
-            }
-    }
-    WsLease l;
-    hipError_t e = hipMalloc((void**)&l.ptr, bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&l.hctrl, sizeof(Ctrl), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        if (l.ptr) (void)hipFree(l.ptr);
-        return set_err(DML_E_HIP, hipGetErrorString(e));
-    }
-    l.bytes = bytes;
-    *out = l;
-    return DML_OK;
-}
-
-static void ws_release(int dev, const WsLease& l) {
-    if (!l.ptr) return;
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    g_ws_free[dev].push_back(l);
-}
-
-// Per-device pool of maxDelta candidate buffers for the AdaGrad chain pieces
-// (dml_prereduce_chain_piece_ada): n candidates plus the finalize's kMdParts of
-// scratch, taken and returned like the workspaces.
-struct CandBuf {
-    DeltaCand* ptr = nullptr;
-    int64_t n = 0;
-};
-static std::unordered_map<int, std::vector<CandBuf>> g_cand_free;
-
-static int cand_acquire(int dev, int64_t n, CandBuf* out) {
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mu);
-        auto& v = g_cand_free[dev];
-        for (size_t i = 0; i < v.size(); ++i)
-            if (v[i].n >= n) {
-                *out = v[i];
-                v.erase(v.begin() + (ptrdiff_t)i);
-                return DML_OK;
-            }
-    }
-    CandBuf b;
-    HIPCHK(hipMalloc((void**)&b.ptr, sizeof(DeltaCand) * (size_t)(n + kMdParts)));
-    b.n = n;
-    *out = b;
-    return DML_OK;
-}
-
-static void cand_release(int dev, const std::vector<CandBuf>& bufs) {
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    for (const CandBuf& b : bufs)
-        if (b.ptr) g_cand_free[dev].push_back(b);
-}
-
-extern "C" {
-
-// Stand-alone ordered pre-reduce (multi-GPU): per-device scratch for Ctrl+slots.
-int dml_reduce_buckets_dense(const dml_desc* desc, int64_t first_key, int64_t rows, int32_t cols,
-                             const void* const* dev_bufs, const int64_t* lens, int32_t n, void* dev_out, void* stream) {
-    if (!desc || !dev_out || rows <= 0 || cols <= 0 || n < 0 || (n > 0 && (!dev_bufs || !lens)))
-        return set_err(DML_E_INVALID_ARG, "bad reduce arguments");
-    if (!push_ptrs_aligned(dev_bufs, n)) return set_err(DML_E_INVALID_ARG, kMisalignedPush);
-    if (desc->data_type != 1 || !desc->dense_column || desc->ada_grad)
-        return set_err(DML_E_UNSUPPORTED, "pre-reduce supports dense-column plain matrices");
-    const int vt = desc->value_type;
-    if (vt != 0 && vt != 1 && vt != 3) return set_err(DML_E_BAD_DESC, "bad value type");
-    const int K = desc->key_type == 0 ? 4 : 8, V = vt == 3 ? 8 : 4;
-    const int64_t stride = K + (int64_t)V * cols;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t sb = (size_t)rows * kMaxW * sizeof(int32_t);
-    const size_t wsb = sizeof(Ctrl) + sb + (size_t)rows * sizeof(uint32_t);
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    WsLease lease;
-    if (int rc = ws_acquire(dev, wsb, &lease)) return rc;
-    uint8_t* ws = lease.ptr;
-    Ctrl* ctrl = (Ctrl*)ws;
-    int32_t* slot = (int32_t*)(ws + sizeof(Ctrl));
-    uint32_t* rflag = (uint32_t*)(ws + sizeof(Ctrl) + sb);
-    AdaArgs none{};
-    int rc = DML_OK;
-    for (int c0 = 0; c0 < std::max(n, 1) && rc == DML_OK; c0 += kMaxW) {
-        Batch bt{};
-        const int nb = std::max(0, std::min(kMaxW, n - c0));
-        int64_t max_nrec = 0;
-        for (int j = 0; j < nb; ++j) {
-            bt.base[j] = (const uint8_t*)dev_bufs[c0 + j];
-            bt.len[j] = lens[c0 + j];
-            bt.nrec[j] = lens[c0 + j] / stride;
-            bt.bidx[j] = c0 + j;
-            if (lens[c0 + j] % stride) rc = set_err(DML_E_TRUNCATED, "ragged full-range bucket");
-            max_nrec = std::max(max_nrec, bt.nrec[j]);
-        }
-        if (rc) break;
-        hipError_t e = hipMemsetAsync(ws, 0xFF, sizeof(Ctrl) + sb, st);
-        if (e == hipSuccess) e = hipMemsetAsync(rflag, 0, (size_t)rows * sizeof(uint32_t), st);
-        if (e == hipSuccess) e = launch_index(bt, nb, max_nrec, stride, K, first_key, rows, slot, rflag, ctrl, kNoPos, st);
-        if (e == hipSuccess)
-            e = launch_reduce(vt, c0 == 0 ? kPreReduce : kAdd, dev_out, rows, cols, bt, nb, stride, K, slot, nullptr,
-                              ctrl, kNoPos, none, st, nullptr);
-        Ctrl h;
-        if (e == hipSuccess) e = hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = set_err(DML_E_HIP, hipGetErrorString(e));
-        else if (h.cutoff != kNoPos) rc = set_err(DML_E_KEY_OUT_OF_SHARD, "pre-reduce: key outside the matrix");
-        else if (h.no_dup == 0u) rc = set_err(DML_E_UNSUPPORTED, "pre-reduce: a bucket repeats a row");
-        if (n == 0) break;
-    }
-    lease.clean = false;  // this path memsets per chunk and does not track cleanliness
-    ws_release(dev, lease);
-    return rc;
-}
-
-// ---- piecewise pre-reduce (multi-GPU pipelining) ----------------------------
-}  // extern "C"
-
-struct dml_prereduce {
-    dml_desc desc{};
-    int64_t first = 0, rows = 0;
-    int32_t cols = 0;
-    int K = 4, V = 4;
-    int64_t stride = 0;
-    Batch bt{};
-    int nb = 0;
-    uint8_t* ws = nullptr;
-    size_t ws_bytes = 0;
-    Ctrl* ctrl = nullptr;
-    int32_t* slot = nullptr;
-    uint32_t* rowflag = nullptr;
-    hipStream_t stream = nullptr;
-    int device = 0;
-    int64_t rows_done = 0;  // model rows the pieces reduced (all of them: the slot table is clean again)
-    Ctrl* hctrl = nullptr;  // the lease's pinned Ctrl copy, DMA'd right behind the index
-    hipEvent_t idx_ev = nullptr;   // begin stream: key index built
-    hipEvent_t last_ev = nullptr;  // piece stream: last piece enqueued so far
-    hipStream_t last_st = nullptr;
-    bool idx_waited = false;
-    bool timed = false;
-    hipEvent_t done_ev = nullptr;  // completion of the last piece: last_ev, or its timing stop event
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;  // per-piece start/stop of a timed call
-    // speculative calls of a pre-reduce context (dml_prereduce_begin_ctx)
-    dml_prectx* ctx = nullptr;
-    int wi = -1;            // the context's workspace
-    bool spec = false;      // identity / kept-column speculation, verified by the pieces
-    bool verified = false;  // dml_prereduce_verify ran (the partial is exact)
-    int64_t max_nrec = 0;
-    struct PieceRec {
-        int64_t block, stride, off, ntask;
-        void* out;
-    };
-    std::vector<PieceRec> prec;  // the pieces as launched (a failed verification re-runs them)
-    hipEvent_t rerun_ev = nullptr;
-    const Ctrl* hidx = nullptr;  // the workspace's Ctrl as the index left it (speculative calls of the flat shape)
-    bool chain_checked = false;  // the first chain piece decided about the up-front identity check
-    bool slots_unread = false;   // that check ran after the index: the pieces leave the filled slot table as it is
-    bool slots_kept = false;     // int32 chain pieces ran: they keep the table for the step's rollback
-    std::vector<CandBuf> cands;  // AdaGrad chain pieces: maxDelta candidates (the last is current), back to the pool at _end
-};
-
-// Pre-reduce context (dml_prectx_*): the sharded path's pre-reduce with the
-// store's speculation. Three workspaces in a ring, like a store's;
-// a verified call keeps its slot table, whose permutations the call three later
-// may reuse. The partial is reduce-scattered only after dml_prereduce_verify has
-// read the pieces' verdict (and re-run them exactly if it failed).
-struct PreWs {
-    uint8_t* base = nullptr;
-    Ctrl* ctrl = nullptr;
-    int32_t* slot = nullptr;
-    uint32_t* rowflag = nullptr;
-    Ctrl* hctrl = nullptr;          // pinned Ctrl, copied after the pieces (or their re-run)
-    Ctrl* hidx = nullptr;           // pinned Ctrl, copied right after the index (k_flat_ident's choice)
-    hipEvent_t ctrl_ev = nullptr;   // that copy done
-    hipEvent_t free_ev = nullptr;   // the workspace's last call ended (pieces / re-run done)
-    bool used = false, clean = false, kept = false;
-    bool busy = false;              // a call holds it: begun, not yet ended
-    int kept_nb = 0;
-    uint64_t perm = 0;              // kept columns holding verified permutations (see Workspace)
-};
-struct dml_prectx {
-    std::mutex mu;
-    dml_desc desc{};
-    int64_t first = 0, rows = 0;
-    int32_t cols = 0;
-    int K = 4, V = 4;
-    int64_t stride = 0;
-    int device = 0;
-    size_t slot_bytes = 0;
-    PreWs ws[kRing];
-    int next = 0;
-    hipStream_t xstream = nullptr;  // Ctrl read-back and re-runs
-    dml_store_counters st{};
-};
-
-// Pre-reduce kernel timing (dml_prereduce_timing(every)): one call in `every`
-// gets start/stop events in its pieces' dispatch packets (events in every packet
-// cost ~10 us per launch: at config 2's 0.4 ms calls, 4 pieces per call would
-// move the step time itself, so bench.py samples 1 in 16 there and every call of
-// config 4's 40 ms calls); _end adds their elapsed time to the totals. Events
-// come from a pool.
-static std::atomic<int32_t> g_pre_timing{0};  // sample one call in g_pre_timing (0 = off)
-static std::atomic<int64_t> g_pre_calls{0};
-static std::mutex g_pre_mu;
-static double g_pre_ms = 0.0;
-static int64_t g_pre_launches = 0;
-static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_pre_pool;
-
-static void prereduce_free(dml_prereduce* p) {
-    if (p->idx_ev) (void)hipEventDestroy(p->idx_ev);
-    if (p->last_ev) (void)hipEventDestroy(p->last_ev);
-    if (p->rerun_ev) (void)hipEventDestroy(p->rerun_ev);
-    delete p;
-}
-
-// ---- what a piece, the int32 close and a failed speculation's re-run share on the host ----
-static RowMap piece_row_map(const dml_prereduce* p, int64_t block, int64_t stride, int64_t off, void* out) {
-    RowMap rm;
-    rm.block = block;
-    rm.stride = stride;
-    rm.off = off;
-    rm.rows_total = p->rows;
-    rm.out = out;
-    return rm;
-}
-// Pieces on another stream (the index ran on a side stream, overlapping the caller's previous
-// work): wait for the index on the host, then enqueue the piece straight behind whatever that
-// stream runs (no cross-queue barrier). And the handle's completion event, on first use.
-static int piece_begin(dml_prereduce* p, hipStream_t st) {
-    if (st != p->stream && !p->idx_waited) {
-        HIPCHK(hipEventSynchronize(p->idx_ev));
-        p->idx_waited = true;
-    }
-    if (!p->last_ev) HIPCHK(hipEventCreateWithFlags(&p->last_ev, hipEventDisableTiming));
-    return DML_OK;
-}
-// A sampled call's (p->timed) start / stop pair for one launch, from the pool; the handle keeps
-// it until dml_prereduce_end has read it.
-static int piece_timing_pair(dml_prereduce* p, std::pair<hipEvent_t, hipEvent_t>* t) {
-    *t = {nullptr, nullptr};
-    {
-        std::lock_guard<std::mutex> lk(g_pre_mu);
-        if (!g_pre_pool.empty()) {
-            *t = g_pre_pool.back();
-            g_pre_pool.pop_back();
-        }
-    }
-    if (!t->first) {
-        HIPCHK(hipEventCreate(&t->first));
-        HIPCHK(hipEventCreate(&t->second));
-    }
-    p->tev.push_back(*t);
-    return DML_OK;
-}
-// model rows a piece covered: blocks of row_block task rows at row_off + q*row_stride
-static void piece_count_rows(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off, int64_t ntask_rows) {
-    for (int64_t t0 = 0; t0 < ntask_rows; t0 += row_block) {
-        const int64_t lo = (t0 / row_block) * row_stride + row_off;
-        const int64_t hi = std::min(lo + std::min(row_block, ntask_rows - t0), p->rows);
-        if (hi > lo) p->rows_done += hi - lo;
-    }
-}
-
-// Read a context call's verdict once its pieces are done; if speculation failed,
-// re-run the call exactly on the context's stream: a fresh slot table, the full
-// key index (repeated rows detected), every recorded piece without speculation.
-static int prereduce_verify(dml_prereduce* p, int32_t* rerun) {
-    if (rerun) *rerun = 0;
-    if (!p->ctx || p->verified) return DML_OK;
-    dml_prectx* x = p->ctx;
-    PreWs& W = x->ws[p->wi];
-    HIPCHK(hipStreamWaitEvent(x->xstream, p->done_ev ? p->done_ev : p->idx_ev, 0));
-    HIPCHK(hipMemcpyAsync(W.hctrl, W.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, x->xstream));
-    HIPCHK(hipEventRecord(W.ctrl_ev, x->xstream));
-    HIPCHK(hipEventSynchronize(W.ctrl_ev));
-    const Ctrl h = *W.hctrl;
-    x->st.chunks += 1;
-    if (p->spec && h.spec_ok != 0u) {
-        x->st.spec_chunks += 1;
-        uint64_t perm = 0;
-        for (int b = 0; b < p->nb; ++b) {
-            if (ctrl_identity(&h, h.ident, b)) {
-                x->st.identity_pushes += 1;
-                continue;
-            }
-            if ((h.ident >> b) & 1ull) x->st.reused_pushes += 1;
-            else x->st.indexed_pushes += 1;
-            perm |= 1ull << ctrl_col(&h, b);
-        }
-        // every row verified: the table's columns are the pushes' permutations
-        if (p->rows_done == p->rows) {
-            W.kept = true;
-            W.kept_nb = p->nb;
-            W.perm = perm;
-        }
-    } else if (p->spec) {
-        x->st.spec_chunks += 1;
-        x->st.spec_reruns += 1;
-        x->st.indexed_pushes += p->nb;
-        Batch bt = p->bt;
-        bt.spec = 0;
-        bt.keeps = 0;
-        bt.kept_cols = 0;
-        bt.ident_ok = 0;
-        bt.prev = nullptr;
-        hipStream_t xs = x->xstream;
-        HIPCHK(hipMemsetAsync(W.base, 0xFF, sizeof(Ctrl) + x->slot_bytes, xs));
-        HIPCHK(hipMemsetAsync(W.rowflag, 0, (size_t)x->rows * sizeof(uint32_t), xs));
-        HIPCHK(launch_index(bt, p->nb, p->max_nrec, p->stride, p->K, p->first, p->rows, W.slot, W.rowflag, W.ctrl,
-                            kNoPos, xs));
-        AdaArgs none{};
-        for (const auto& pr : p->prec) {
-            const RowMap rm = piece_row_map(p, pr.block, pr.stride, pr.off, pr.out);
-            HIPCHK(launch_reduce(p->desc.value_type, kPreReduce, pr.out, pr.ntask, p->cols, bt, p->nb, p->stride,
-                                 p->K, W.slot, nullptr, W.ctrl, kNoPos, none, xs, nullptr, LaunchEv{}, rm));
-        }
-        if (!p->rerun_ev) HIPCHK(hipEventCreateWithFlags(&p->rerun_ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(p->rerun_ev, xs));
-        p->done_ev = p->rerun_ev;  // consumers of the partial (dml_prereduce_stream_wait) wait for the re-run
-        HIPCHK(hipMemcpyAsync(W.hctrl, W.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, xs));
-        HIPCHK(hipEventRecord(W.ctrl_ev, xs));
-        p->bt = bt;
-        p->spec = false;
-        if (rerun) *rerun = 1;
-    } else {
-        for (int b = 0; b < p->nb; ++b) {
-            if (p->bt.ident_ok && ((h.ident >> b) & 1ull)) x->st.identity_pushes += 1;
-            else x->st.indexed_pushes += 1;
-        }
-    }
-    p->verified = true;
-    return DML_OK;
-}
-
-extern "C" {
-
-int dml_prereduce_begin(const dml_desc* desc, int64_t first_key, int64_t rows, int32_t cols, const void* const* dev_bufs,
-                        const int64_t* lens, int32_t n, void* stream, dml_prereduce** out) {
-    if (!desc || !out || rows <= 0 || cols <= 0 || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
-        return set_err(DML_E_INVALID_ARG, "bad pre-reduce arguments (n must be <= 64)");
-    if (!push_ptrs_aligned(dev_bufs, n)) return set_err(DML_E_INVALID_ARG, kMisalignedPush);
-    // AdaGrad matrices: only the two-moment pieces (dml_prereduce_moments_piece)
-    if (desc->data_type != 1 || !desc->dense_column || (desc->ada_grad && desc->value_type != DML_ELEMENT_TYPE_FLOAT))
-        return set_err(DML_E_UNSUPPORTED, "pre-reduce supports dense-column matrices");
-    if (desc->value_type != 0 && desc->value_type != 1 && desc->value_type != 3)
-        return set_err(DML_E_BAD_DESC, "bad value type");
-    auto* p = new (std::nothrow) dml_prereduce();
-    if (!p) return set_err(DML_E_NOMEM, "out of host memory");
-    p->desc = *desc;
-    p->first = first_key;
-    p->rows = rows;
-    p->cols = cols;
-    p->K = desc->key_type == 0 ? 4 : 8;
-    p->V = desc->value_type == 3 ? 8 : 4;
-    p->stride = p->K + (int64_t)p->V * cols;
-    p->stream = (hipStream_t)stream;
-    HIPCHK(hipGetDevice(&p->device));
-    int64_t max_nrec = 0;
-    for (int j = 0; j < n; ++j) {
-        if (lens[j] % p->stride) {
-            delete p;
-            return set_err(DML_E_TRUNCATED, "ragged full-range push");
-        }
-        p->bt.base[j] = (const uint8_t*)dev_bufs[j];
-        p->bt.len[j] = lens[j];
-        p->bt.nrec[j] = lens[j] / p->stride;
-        p->bt.bidx[j] = j;
-        max_nrec = std::max(max_nrec, p->bt.nrec[j]);
-    }
-    p->nb = n;
-    const size_t sb = (size_t)rows * kMaxW * sizeof(int32_t);
-    WsLease lease;
-    if (int rc = ws_acquire(p->device, sizeof(Ctrl) + sb + (size_t)rows * sizeof(uint32_t), &lease)) {
-        delete p;
-        return rc;
-    }
-    p->ws = lease.ptr;
-    p->ws_bytes = lease.bytes;
-    p->hctrl = lease.hctrl;
-    const bool clean = lease.clean && lease.clean_rows == rows;
-    p->ctrl = (Ctrl*)p->ws;
-    p->slot = (int32_t*)(p->ws + sizeof(Ctrl));
-    p->rowflag = (uint32_t*)(p->ws + sizeof(Ctrl) + sb);
-    // a clean lease needs only its Ctrl reset (see launch_chunk)
-    hipError_t e = hipMemsetAsync(p->ws, 0xFF, sizeof(Ctrl) + (clean ? 0 : sb), p->stream);
-    if (e == hipSuccess && !clean) e = hipMemsetAsync(p->rowflag, 0, (size_t)rows * sizeof(uint32_t), p->stream);
-    // Full-range pushes whose records are rows in order (Java HashMap<Integer> order)
-    // skip the key index: every key is checked (k_ident_full) before the pieces,
-    // which take slot = row for them. Complete rather than speculative: the
-    // reduce-scatter reads the partial as soon as a piece is done. Only for slot
-    // tables beyond the caches, where the index's slot atomics go to DRAM (config
-    // 4 at N > 1: 160 M records, a 640 MB table; world-1 group path 40.8 -> 36.7
-    // ms/call): for config 2's 2 MB table the complete check reads as many key
-    // lines as the index and lengthens the index stream's chain, which must end
-    // before the running pre-reduce does (0.450 -> 0.490 ms/call, measured).
-    bool full = n > 0 && (int64_t)rows * slot_stride(n) * 4 > ((int64_t)64 << 20);
-    for (int j = 0; j < n && full; ++j) full = p->bt.nrec[j] == rows;
-    p->bt.first = first_key;
-    if (e == hipSuccess && full) {
-        e = launch_ident_full(p->bt, n, max_nrec, p->stride, p->K, first_key, rows, p->ctrl, p->stream);
-        p->bt.ident_ok = 1;
-    }
-    if (e == hipSuccess)
-        e = launch_index(p->bt, n, max_nrec, p->stride, p->K, first_key, rows, p->slot, p->rowflag, p->ctrl, kNoPos,
-                         p->stream);
-    // the index alone writes the Ctrl: copy it out now, so _end reads it without
-    // queueing anything behind the caller's later work
-    if (e == hipSuccess) e = hipMemcpyAsync(p->hctrl, p->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->idx_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(p->idx_ev, p->stream);
-    if (e != hipSuccess) {
-        // the stream may still reference the workspace: drain it before reuse
-        (void)hipStreamSynchronize(p->stream);
-        ws_release(p->device, WsLease{p->ws, p->ws_bytes, false, p->hctrl});
-        prereduce_free(p);
-        return set_err(DML_E_HIP, hipGetErrorString(e));
-    }
-    const int32_t every = g_pre_timing.load(std::memory_order_relaxed);
-    p->timed = every > 0 && g_pre_calls.fetch_add(1, std::memory_order_relaxed) % every == 0;
-    *out = p;
-    return DML_OK;
-}
-
-int dml_prereduce_moments_piece(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
-                                int64_t ntask_rows, void* dev_out, void* stream) {
-    if (!p || !dev_out || row_block <= 0 || ntask_rows < 0) return set_err(DML_E_INVALID_ARG, "bad piece arguments");
-    if (p->ctx || p->desc.value_type != DML_ELEMENT_TYPE_FLOAT || p->cols % 4 || p->cols * 4 >= 4096)
-        return set_err(DML_E_UNSUPPORTED, "two-moment pieces: f32 rows of whole 16-B vectors under 4 KiB");
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = piece_begin(p, st)) return rc;
-    const RowMap rm = piece_row_map(p, row_block, row_stride, row_off, dev_out);
-    HIPCHK(launch_moments(ntask_rows, p->cols, p->bt, p->nb, p->stride, p->K, p->slot, p->ctrl, rm, st,
-                          LaunchEv{nullptr, p->last_ev}));
-    p->done_ev = p->last_ev;
-    piece_count_rows(p, row_block, row_stride, row_off, ntask_rows);
-    p->last_st = st;
-    return DML_OK;
-}
-
-}  // extern "C"
-
-// One piece of a pre-reduce handle: `mode` kPreReduce (dml_prereduce_piece: sums from
-// zero) or kChain (dml_prereduce_chain_piece: sums onto dev_base, a chained
-// reduce-scatter step). Row map, stream rule, completion event and timing are shared.
-struct AdaPiece {
-    const void* base_delta;
-    const void* base_marks;
-    void* out_delta;
-    void* out_marks;
-    void* record;  // the slice's travelling MaxDelta
-    bool last;     // last piece of this rank's step over the slice
-};
-static int prereduce_piece(dml_prereduce* p, int mode, int64_t row_block, int64_t row_stride, int64_t row_off,
-                           int64_t ntask_rows, const void* dev_base, void* dev_out, void* stream,
-                           const AdaPiece* ap = nullptr, const void* dev_record = nullptr) {
-    hipStream_t st = (hipStream_t)stream;  // as given: 0 is HIP's null stream
-    if (mode == kChain && !p->chain_checked) {
-        // Ascending full-range pushes of a flat shape (config 4's case): verify every
-        // key up front (k_ident_full), behind the index on its stream, so the pieces
-        // take slot = row and, once the host has seen the verdict, k_flat_ident.
-        // Complete, not speculative: a chained slice leaves the rank when its piece
-        // ends. (dml_prereduce_begin does this itself for slot tables beyond the
-        // caches; the table the index filled is then not read, so it is not clean.)
-        p->chain_checked = true;
-        bool full = p->nb > 0 && !p->bt.ident_ok && use_flat(p->desc.value_type, kChain, p->cols, p->bt, p->nb, p->rows);
-        for (int j = 0; j < p->nb && full; ++j) full = p->bt.nrec[j] == p->rows;
-        if (full) {
-            HIPCHK(launch_ident_full(p->bt, p->nb, p->rows, p->stride, p->K, p->first, p->rows, p->ctrl, p->stream));
-            p->bt.ident_ok = 1;
-            p->slots_unread = true;
-            HIPCHK(hipMemcpyAsync(p->hctrl, p->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, p->stream));
-            HIPCHK(hipEventRecord(p->idx_ev, p->stream));
-            p->idx_waited = false;
-        }
-        if (p->bt.ident_ok) p->hidx = p->hctrl;  // the verdict k_flat_ident is chosen from
-    }
-    if (int rc = piece_begin(p, st)) return rc;
-    RowMap rm = piece_row_map(p, row_block, row_stride, row_off, dev_out);
-    rm.base = dev_base;
-    rm.rec = dev_record;
-    if (mode == kChainCheckI32) p->slots_kept = true;
-    AdaArgs none{};
-    // the piece's completion event rides in its dispatch packet (no marker packet between pieces)
-    LaunchEv ev{nullptr, p->last_ev};
-    if (ap) ev.stop = nullptr;  // the candidates' finalize follows the kernel: last_ev is recorded behind it
-    if (p->timed) {  // both timing events ride in the packet too
-        std::pair<hipEvent_t, hipEvent_t> t;
-        if (int rc = piece_timing_pair(p, &t)) return rc;
-        ev = LaunchEv{t.first, t.second};
-    }
-    // all-identity calls (seen in the index's Ctrl, once the host has waited for it):
-    // the lean kernel, when no wave's rows straddle two row blocks of the map
-    const int Rw = flat_ident_rows_per_wave(p->desc.value_type, p->cols);
-    if (ap) {
-        // the vector stream needs no whole waves per row block (its row map is per vector)
-        const bool ident = p->hidx && p->idx_waited && flat_ident_ok(*p->hidx, p->bt, p->nb, p->rows, kNoPos);
-        const int64_t need = std::max<int64_t>(1, chain_ada_blocks(ident, ntask_rows, p->cols));
-        if (p->cands.empty() || p->cands.back().n < need) {
-            CandBuf cb;
-            if (int rc = cand_acquire(p->device, need, &cb)) return rc;
-            p->cands.push_back(cb);
-        }
-        ChainAda ca{(const float*)ap->base_delta, (float*)ap->out_delta, (const uint32_t*)ap->base_marks,
-                    (uint32_t*)ap->out_marks, p->cands.back().ptr};
-        int64_t ncand = 0;
-        HIPCHK(launch_chain_ada(ident, ntask_rows, p->cols, p->bt, p->nb, p->stride, p->K, p->slot, p->ctrl, rm, ca, st,
-                                &ncand, ev));
-        // this piece's candidates into the record's pending one; the step's last piece applies
-        // the strict > against the earlier ranks once (ties inside the rank: earlier position)
-        HIPCHK(launch_maxdelta_finalize(ca.cand, ncand, (MaxDelta*)ap->record, p->bt, p->nb, p->stride, p->K, p->V, st,
-                                        ap->last ? kMdApply : kMdDefer));
-        HIPCHK(hipEventRecord(p->last_ev, st));
-        ev.stop = p->last_ev;
-    } else if (p->hidx && p->idx_waited && (row_block % Rw == 0 || ntask_rows <= row_block) &&
-        flat_ident_ok(*p->hidx, p->bt, p->nb, p->rows, kNoPos)) {
-        if (p->ctx) {
-            std::lock_guard<std::mutex> lk(p->ctx->mu);
-            p->ctx->st.ident_launches += 1;
-        }
-        HIPCHK(launch_flat_ident(p->desc.value_type, mode, dev_out, ntask_rows, p->cols, p->bt, p->nb, p->stride,
-                                 p->K, p->ctrl, st, nullptr, ev, rm));
-    } else
-        HIPCHK(launch_reduce(p->desc.value_type, mode, dev_out, ntask_rows, p->cols, p->bt, p->nb, p->stride,
-                             p->K, p->slot, nullptr, p->ctrl, kNoPos, none, st, nullptr, ev, rm));
-    p->done_ev = ev.stop;
-    if (mode == kPreReduce) p->prec.push_back({row_block, row_stride, row_off, ntask_rows, dev_out});
-    piece_count_rows(p, row_block, row_stride, row_off, ntask_rows);
-    p->last_st = st;
-    return DML_OK;
-}
-
-extern "C" {
-
-int dml_prereduce_piece(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off, int64_t ntask_rows,
-                        void* dev_out, void* stream) {
-    if (!p || !dev_out || row_block <= 0 || ntask_rows < 0) return set_err(DML_E_INVALID_ARG, "bad piece arguments");
-    if (p->desc.ada_grad) return set_err(DML_E_UNSUPPORTED, "AdaGrad pre-reduce: dml_prereduce_moments_piece");
-    return prereduce_piece(p, kPreReduce, row_block, row_stride, row_off, ntask_rows, nullptr, dev_out, stream);
-}
-
-int dml_prereduce_chain_piece(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
-                              int64_t ntask_rows, const void* dev_base, void* dev_out, void* stream) {
-    if (!p || !dev_base || !dev_out || row_block <= 0 || ntask_rows < 0)
-        return set_err(DML_E_INVALID_ARG, "bad chain piece arguments");
-    if (p->desc.ada_grad || (p->desc.value_type != DML_ELEMENT_TYPE_FLOAT && p->desc.value_type != DML_ELEMENT_TYPE_DOUBLE))
-        return set_err(DML_E_UNSUPPORTED,
-                       "chained pieces: plain fp32 / fp64 matrices (int32 and AdaGrad: dml_group_push_exchange)");
-    // what a chain piece writes is forwarded at once: a speculative handle's verdict
-    // (dml_prereduce_verify) would come after the slice has left the rank
-    if (p->ctx) return set_err(DML_E_UNSUPPORTED, "chained pieces need dml_prereduce_begin (no speculative context)");
-    return prereduce_piece(p, kChain, row_block, row_stride, row_off, ntask_rows, dev_base, dev_out, stream);
-}
-
-int dml_prereduce_chain_piece_ada(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
-                                  int64_t ntask_rows, const void* base_data, const void* base_delta,
-                                  const void* base_marks, void* out_data, void* out_delta, void* out_marks,
-                                  void* maxdelta_record, int32_t last_piece, void* stream) {
-    if (!p || !base_data || !base_delta || !out_data || !out_delta || !out_marks || !maxdelta_record || row_block <= 0 ||
-        ntask_rows < 0)
-        return set_err(DML_E_INVALID_ARG, "bad AdaGrad chain piece arguments");
-    if (!p->desc.ada_grad || p->desc.value_type != DML_ELEMENT_TYPE_FLOAT)
-        return set_err(DML_E_UNSUPPORTED,
-                       "AdaGrad chained pieces: a handle begun with the AdaGrad descriptor (plain fp32 / fp64: "
-                       "dml_prereduce_chain_piece; int32: dml_group_push_exchange)");
-    if (p->ctx) return set_err(DML_E_UNSUPPORTED, "chained pieces need dml_prereduce_begin (no speculative context)");
-    const AdaPiece ap{base_delta, base_marks, out_delta, out_marks, maxdelta_record, last_piece != 0};
-    return prereduce_piece(p, kChain, row_block, row_stride, row_off, ntask_rows, base_data, out_data, stream, &ap);
-}
-
-static int chain_i32_refusal(const dml_prereduce* p) {
-    if (p->desc.ada_grad || p->desc.value_type != DML_ELEMENT_TYPE_INT)
-        return set_err(DML_E_UNSUPPORTED,
-                       "int32 chained pieces: a dense int32 matrix handle (fp32 / fp64: dml_prereduce_chain_piece; "
-                       "AdaGrad: dml_prereduce_chain_piece_ada)");
-    // the slice leaves the rank right after the step's close: a speculative handle's
-    // verdict (dml_prereduce_verify) would come later
-    if (p->ctx) return set_err(DML_E_UNSUPPORTED, "chained pieces need dml_prereduce_begin (no speculative context)");
-    return DML_OK;
-}
-
-int dml_prereduce_chain_piece_i32(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
-                                  int64_t ntask_rows, const void* dev_base, void* dev_out, const void* dev_record,
-                                  void* stream) {
-    if (!p || !dev_base || !dev_out || !dev_record || ((uintptr_t)dev_record & 7u) || row_block <= 0 || ntask_rows < 0)
-        return set_err(DML_E_INVALID_ARG, "bad int32 chain piece arguments");
-    if (int rc = chain_i32_refusal(p)) return rc;
-    return prereduce_piece(p, kChainCheckI32, row_block, row_stride, row_off, ntask_rows, dev_base, dev_out, stream,
-                           nullptr, dev_record);
-}
-
-int dml_prereduce_chain_close_i32(dml_prereduce* p, int64_t row_block, int64_t row_stride, int64_t row_off,
-                                  int64_t ntask_rows, void* dev_slice, void* dev_record, int32_t ring_step,
-                                  void* stream) {
-    if (!p || !dev_slice || !dev_record || ((uintptr_t)dev_record & 7u) || row_block <= 0 || ntask_rows < 0 ||
-        ring_step < 0)
-        return set_err(DML_E_INVALID_ARG, "bad int32 chain close arguments");
-    if (int rc = chain_i32_refusal(p)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = piece_begin(p, st)) return rc;
-    const RowMap rm = piece_row_map(p, row_block, row_stride, row_off, dev_slice);
-    LaunchEv ev{nullptr, p->last_ev};
-    if (p->timed) {
-        // two launches under one pair: the start event is recorded ahead of the rollback, not
-        // put into a packet as the pieces do; the stop event rides in the verdict's
-        std::pair<hipEvent_t, hipEvent_t> t;
-        if (int rc = piece_timing_pair(p, &t)) return rc;
-        HIPCHK(hipEventRecord(t.first, st));
-        ev.stop = t.second;
-    }
-    // undo, mod 2^32, this rank's adds past the step's first negative (waves leave at
-    // once while Ctrl::neg_pos is kNoPos), then the verdict: one launch each per step
-    if (ntask_rows > 0 && p->nb > 0)
-        HIPCHK(launch_rollback_i32((int32_t*)dev_slice, ntask_rows, p->cols, p->bt, p->nb, p->stride, p->K, p->slot,
-                                   nullptr, p->ctrl, kNoPos, st, rm));
-    HIPCHK(launch_chain_i32_verdict(p->bt, p->nb, p->stride, p->K, p->ctrl, (ChainI32Rec*)dev_record, ring_step, st, ev));
-    p->done_ev = ev.stop;
-    p->last_st = st;
-    return DML_OK;
-}
-
-int dml_prereduce_timing(int32_t every) {
-    g_pre_timing.store(every > 0 ? every : 0);
-    g_pre_calls.store(0);
-    return DML_OK;
-}
-
-int dml_prereduce_kernel_time(double* ms, int64_t* launches, int32_t reset) {
-    if (!ms || !launches) return set_err(DML_E_INVALID_ARG, "null output");
-    std::lock_guard<std::mutex> lk(g_pre_mu);
-    *ms = g_pre_ms;
-    *launches = g_pre_launches;
-    if (reset) {
-        g_pre_ms = 0.0;
-        g_pre_launches = 0;
-    }
-    return DML_OK;
-}
-
-int dml_prereduce_stream_wait(dml_prereduce* p, void* stream) {
-    if (!p || !p->done_ev) return set_err(DML_E_INVALID_ARG, "no piece enqueued yet");
-    HIPCHK(hipStreamWaitEvent((hipStream_t)stream, p->done_ev, 0));
-    return DML_OK;
-}
-
-int dml_prereduce_verify(dml_prereduce* p, int32_t* rerun) {
-    if (!p) return set_err(DML_E_INVALID_ARG, "null pre-reduce");
-    if (!p->ctx) {  // a call without a context does not speculate
-        if (rerun) *rerun = 0;
-        return DML_OK;
-    }
-    std::lock_guard<std::mutex> lk(p->ctx->mu);
-    return prereduce_verify(p, rerun);
-}
-
-int dml_prereduce_end(dml_prereduce* p) {
-    if (!p) return set_err(DML_E_INVALID_ARG, "null pre-reduce");
-    if (p->ctx) {
-        dml_prectx* x = p->ctx;
-        std::lock_guard<std::mutex> lk(x->mu);
-        PreWs& W = x->ws[p->wi];
-        int rc = prereduce_verify(p, nullptr);
-        hipError_t e = rc == DML_OK ? hipEventSynchronize(W.ctrl_ev) : hipErrorUnknown;  // pieces / re-run done
-        const Ctrl h = *W.hctrl;
-        if (!p->tev.empty()) {
-            double ms = 0.0;
-            for (auto& t : p->tev) {
-                float v = 0.f;
-                if (e == hipSuccess && hipEventElapsedTime(&v, t.first, t.second) == hipSuccess) ms += v;
-            }
-            std::lock_guard<std::mutex> lk2(g_pre_mu);
-            if (e == hipSuccess) {
-                g_pre_ms += ms;
-                g_pre_launches += (int64_t)p->tev.size();
-            }
-            g_pre_pool.insert(g_pre_pool.end(), p->tev.begin(), p->tev.end());
-            p->tev.clear();
-        }
-        if (rc == DML_OK && e != hipSuccess) rc = set_err(DML_E_HIP, hipGetErrorString(e));
-        else if (rc == DML_OK && h.cutoff != kNoPos) rc = set_err(DML_E_KEY_OUT_OF_SHARD, "pre-reduce: key outside the matrix");
-        else if (rc == DML_OK && h.no_dup == 0u) rc = set_err(DML_E_UNSUPPORTED, "pre-reduce: a push repeats a row");
-        // a kept table stays (not clean); a non-speculative call whose pieces covered every
-        // row through the clearing kernel left it clean; anything else is memset next time
-        W.clean = !W.kept && !p->spec && rc == DML_OK && p->rows_done == p->rows &&
-                  reduce_clears_slots(p->desc.value_type, kPreReduce, p->cols);
-        if (rc != DML_OK) W.kept = false;
-        (void)hipEventRecord(W.free_ev, x->xstream);
-        W.busy = false;
-        prereduce_free(p);
-        return rc;
-    }
-    hipError_t e = hipEventSynchronize(p->idx_ev);  // index done, Ctrl copied out
-    const Ctrl h = *p->hctrl;
-    // the workspace is free once the last piece ran
-    if (e == hipSuccess && p->done_ev) e = hipEventSynchronize(p->done_ev);
-    if (!p->tev.empty()) {
-        double ms = 0.0;
-        for (auto& t : p->tev) {
-            float x = 0.f;
-            if (e == hipSuccess && hipEventElapsedTime(&x, t.first, t.second) == hipSuccess) ms += x;
-        }
-        std::lock_guard<std::mutex> lk(g_pre_mu);
-        if (e == hipSuccess) {
-            g_pre_ms += ms;
-            g_pre_launches += (int64_t)p->tev.size();
-        }
-        g_pre_pool.insert(g_pre_pool.end(), p->tev.begin(), p->tev.end());
-        p->tev.clear();
-    }
-    int rc = DML_OK;
-    if (e != hipSuccess) rc = set_err(DML_E_HIP, hipGetErrorString(e));
-    else if (h.cutoff != kNoPos) rc = set_err(DML_E_KEY_OUT_OF_SHARD, "pre-reduce: key outside the matrix");
-    else if (h.no_dup == 0u) rc = set_err(DML_E_UNSUPPORTED, "pre-reduce: a push repeats a row");
-    // after a failed sync the device state is unknown: drop the lease. A normal chunk
-    // whose pieces reduced every row through the clearing kernel left the table clean.
-    // (a chained call's late identity check: the pushes it confirmed left their indexed
-    // slots unread and uncleared; pushes it rejected were read and cleared like any other)
-    const uint64_t pushes = p->nb >= 64 ? ~0ull : (1ull << p->nb) - 1ull;
-    if (p->slots_unread && !(h.ident & pushes)) p->slots_unread = false;
-    const bool clean = rc == DML_OK && !p->slots_unread && !p->slots_kept && p->rows_done == p->rows &&
-                       reduce_clears_slots(p->desc.value_type, kPreReduce, p->cols);
-    if (e == hipSuccess) ws_release(p->device, WsLease{p->ws, p->ws_bytes, clean, p->hctrl, p->rows});
-    if (e == hipSuccess) cand_release(p->device, p->cands);
-    prereduce_free(p);
-    return rc;
-}
-
-int dml_prectx_create(const dml_desc* desc, int64_t first_key, int64_t rows, int32_t cols, int32_t device,
-                      dml_prectx** out) {
-    if (!desc || !out || rows <= 0 || cols <= 0) return set_err(DML_E_INVALID_ARG, "bad pre-reduce context arguments");
-    *out = nullptr;
-    if (desc->data_type != 1 || !desc->dense_column || desc->ada_grad)
-        return set_err(DML_E_UNSUPPORTED, "pre-reduce supports dense-column plain matrices");
-    if (desc->value_type != 0 && desc->value_type != 1 && desc->value_type != 3)
-        return set_err(DML_E_BAD_DESC, "bad value type");
-    if (rows > INT32_MAX) return set_err(DML_E_INVALID_ARG, "matrix larger than a Java array");
-    DeviceGuard g(device);
-    auto* x = new (std::nothrow) dml_prectx();
-    if (!x) return set_err(DML_E_NOMEM, "out of host memory");
-    x->desc = *desc;
-    x->first = first_key;
-    x->rows = rows;
-    x->cols = cols;
-    x->K = desc->key_type == 0 ? 4 : 8;
-    x->V = desc->value_type == 3 ? 8 : 4;
-    x->stride = x->K + (int64_t)x->V * cols;
-    x->device = device;
-    x->slot_bytes = (size_t)rows * kMaxW * sizeof(int32_t);
-    auto fail = [&](hipError_t e) {
-        dml_prectx_destroy(x);
-        return set_err(DML_E_HIP, std::string("pre-reduce context: ") + hipGetErrorString(e));
-    };
-    hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&x->xstream, hipStreamNonBlocking)) != hipSuccess) return fail(e);
-    for (PreWs& W : x->ws) {
-        if ((e = hipMalloc((void**)&W.base, sizeof(Ctrl) + x->slot_bytes + (size_t)rows * sizeof(uint32_t))) !=
-            hipSuccess)
-            return fail(e);
-        W.ctrl = (Ctrl*)W.base;
-        W.slot = (int32_t*)(W.base + sizeof(Ctrl));
-        W.rowflag = (uint32_t*)(W.base + sizeof(Ctrl) + x->slot_bytes);
-        if ((e = hipHostMalloc((void**)&W.hctrl, sizeof(Ctrl), hipHostMallocDefault)) != hipSuccess) return fail(e);
-        if ((e = hipEventCreateWithFlags(&W.ctrl_ev, hipEventDisableTiming)) != hipSuccess) return fail(e);
-        if ((e = hipEventCreateWithFlags(&W.free_ev, hipEventDisableTiming)) != hipSuccess) return fail(e);
-    }
-    *out = x;
-    return DML_OK;
-}
-
-void dml_prectx_destroy(dml_prectx* x) {
-    if (!x) return;
-    {
-        std::lock_guard<std::mutex> lk(x->mu);
-        DeviceGuard g(x->device);
-        if (x->xstream) (void)hipStreamSynchronize(x->xstream);
-        for (PreWs& W : x->ws) {
-            if (W.free_ev) (void)hipEventSynchronize(W.free_ev);
-            (void)hipFree(W.base);
-            if (W.hidx) (void)hipHostFree(W.hidx);
-            if (W.hctrl) (void)hipHostFree(W.hctrl);
-            if (W.ctrl_ev) (void)hipEventDestroy(W.ctrl_ev);
-            if (W.free_ev) (void)hipEventDestroy(W.free_ev);
-        }
-        if (x->xstream) (void)hipStreamDestroy(x->xstream);
-    }
-    delete x;
-}
-
-int dml_prectx_stats(dml_prectx* x, dml_store_counters* out, int32_t reset) {
-    if (!x || !out) return set_err(DML_E_INVALID_ARG, "null argument");
-    std::lock_guard<std::mutex> lk(x->mu);
-    *out = x->st;
-    if (reset) x->st = dml_store_counters{};
-    return DML_OK;
-}
-
-int dml_prereduce_begin_ctx(dml_prectx* x, const void* const* dev_bufs, const int64_t* lens, int32_t n, void* stream,
-                            dml_prereduce** out) {
-    if (!x || !out || n < 0 || n > kMaxW || (n > 0 && (!dev_bufs || !lens)))
-        return set_err(DML_E_INVALID_ARG, "bad pre-reduce arguments (n must be <= 64)");
-    if (!push_ptrs_aligned(dev_bufs, n)) return set_err(DML_E_INVALID_ARG, kMisalignedPush);
-    std::lock_guard<std::mutex> lk(x->mu);
-    DeviceGuard g(x->device);
-    // the ring's next workspace must have been ended: a call still holding it would
-    // have its Ctrl and slot table rewritten under its pieces
-    if (x->ws[x->next].busy)
-        return set_err(DML_E_INVALID_ARG, "three calls of this pre-reduce context are outstanding: end one first");
-    auto* p = new (std::nothrow) dml_prereduce();
-    if (!p) return set_err(DML_E_NOMEM, "out of host memory");
-    p->desc = x->desc;
-    p->first = x->first;
-    p->rows = x->rows;
-    p->cols = x->cols;
-    p->K = x->K;
-    p->V = x->V;
-    p->stride = x->stride;
-    p->stream = (hipStream_t)stream;
-    p->device = x->device;
-    for (int j = 0; j < n; ++j) {
-        if (lens[j] % p->stride) {
-            delete p;
-            return set_err(DML_E_TRUNCATED, "ragged full-range push");
-        }
-        p->bt.base[j] = (const uint8_t*)dev_bufs[j];
-        p->bt.len[j] = lens[j];
-        p->bt.nrec[j] = lens[j] / p->stride;
-        p->bt.bidx[j] = j;
-        p->max_nrec = std::max(p->max_nrec, p->bt.nrec[j]);
-    }
-    p->nb = n;
-    p->bt.first = x->first;
-    const int wi = x->next;
-    x->next = (x->next + 1) % kRing;
-    PreWs& W = x->ws[wi];
-    p->ctx = x;
-    p->wi = wi;
-    p->ws = W.base;
-    p->ctrl = W.ctrl;
-    p->slot = W.slot;
-    p->rowflag = W.rowflag;
-    p->hctrl = W.hctrl;
-    const int vt = x->desc.value_type;
-    bool full = n > 0;
-    for (int j = 0; j < n && full; ++j) full = p->bt.nrec[j] == x->rows;
-    // full-range pushes of the speculation shapes: identity / kept-column pushes skip
-    // the key index and the pieces verify every record (a failure re-runs the call)
-    p->spec = full && spec_shape(vt, x->cols);
-    p->bt.spec = p->bt.keeps = p->spec ? 1 : 0;
-    p->bt.kept_cols = (p->spec && W.kept && slot_stride(W.kept_nb) == slot_stride(n)) ? W.perm : 0;
-    hipStream_t st = p->stream;
-    hipError_t e = hipSuccess;
-    if (W.used) e = hipStreamWaitEvent(st, W.free_ev, 0);  // its last call's pieces / re-run
-    const bool slots_ok = W.clean || (W.kept && p->spec);
-    if (e == hipSuccess) e = hipMemsetAsync(W.base, 0xFF, sizeof(Ctrl) + (slots_ok ? 0 : x->slot_bytes), st);
-    if (e == hipSuccess && !(W.clean || W.kept)) e = hipMemsetAsync(W.rowflag, 0, (size_t)x->rows * sizeof(uint32_t), st);
-    W.clean = W.kept = false;
-    W.used = true;
-    W.busy = true;
-    if (e == hipSuccess && p->spec) {
-        e = launch_ident_check(p->bt, n, p->stride, p->K, x->first, x->rows, W.slot, W.ctrl, st);
-        if (e == hipSuccess && p->bt.kept_cols) e = launch_assign_cols(W.ctrl, n, st);
-    } else if (e == hipSuccess && full && (int64_t)x->rows * slot_stride(n) * 4 > ((int64_t)64 << 20)) {
-        // other shapes: the complete identity check of dml_prereduce_begin
-        e = launch_ident_full(p->bt, n, p->max_nrec, p->stride, p->K, x->first, x->rows, W.ctrl, st);
-        p->bt.ident_ok = 1;
-    }
-    if (e == hipSuccess)
-        e = launch_index(p->bt, n, p->max_nrec, p->stride, p->K, x->first, x->rows, W.slot, W.rowflag, W.ctrl, kNoPos,
-                         st);
-    // speculative calls of the flat shape: a pinned copy of the Ctrl the index left, so
-    // that the pieces (after the host's wait for the index) can run k_flat_ident
-    p->hidx = nullptr;
-    if (e == hipSuccess && p->spec && use_flat(vt, kPreReduce, x->cols, p->bt, n, x->rows)) {
-        if (!W.hidx) e = hipHostMalloc((void**)&W.hidx, sizeof(Ctrl), hipHostMallocDefault);
-        if (e == hipSuccess) {
-            W.hidx->cutoff = 0;  // not all-identity unless the copy lands
-            e = hipMemcpyAsync(W.hidx, W.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, st);
-            p->hidx = W.hidx;
-        }
-    }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->idx_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(p->idx_ev, st);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        (void)hipEventRecord(W.free_ev, st);
-        W.busy = false;
-        prereduce_free(p);
-        return set_err(DML_E_HIP, hipGetErrorString(e));
-    }
-    const int32_t every = g_pre_timing.load(std::memory_order_relaxed);
-    p->timed = every > 0 && g_pre_calls.fetch_add(1, std::memory_order_relaxed) % every == 0;
-    *out = p;
-    return DML_OK;
-}
-
 // ---- synthetic data --------------------------------------------------------
 int dml_synth_dense_bucket(void* dev_out, const dml_desc* desc, int64_t first_key, int64_t shard_rows, int64_t nrec,
                            int32_t cols, uint64_t seed, uint64_t perm_a, uint64_t perm_c, void* stream) {
     if (!dev_out || !desc || shard_rows <= 0 || nrec < 0 || cols <= 0) return set_err(DML_E_INVALID_ARG, "bad synth args");
     if (perm_a >= (1ull << 32) || (uint64_t)nrec >= (1ull << 32)) return set_err(DML_E_INVALID_ARG, "perm_a/nrec must be < 2^32");
-    const int K = desc->key_type == 0 ? 4 : 8;
+    const int K = desc_key_bytes(*desc);
     HIPCHK(launch_synth_dense((uint8_t*)dev_out, K, desc->value_type, first_key, shard_rows, nrec, cols,
                               splitmix64(seed), perm_a % (uint64_t)shard_rows, perm_c % (uint64_t)shard_rows,
                               (hipStream_t)stream));
@@ -2827,8 +1863,8 @@ int dml_synth_sparse_bucket(void* dev_out, const dml_desc* desc, int64_t first_k
                             uint64_t seed, uint64_t perm_a, uint64_t perm_c, void* stream) {
     if (!dev_out || !desc || key_space <= 0 || nrec < 0) return set_err(DML_E_INVALID_ARG, "bad synth args");
     if (perm_a >= (1ull << 32) || (uint64_t)nrec >= (1ull << 32)) return set_err(DML_E_INVALID_ARG, "perm_a/nrec must be < 2^32");
-    const int K = desc->key_type == 0 ? 4 : 8;
-    const int V = desc->value_type == DML_ELEMENT_TYPE_DOUBLE ? 8 : 4;
+    const int K = desc_key_bytes(*desc);
+    const int V = desc_value_bytes(*desc);
     HIPCHK(launch_synth_sparse((uint8_t*)dev_out, K, desc->value_type, V, first_key, key_space, nrec, splitmix64(seed),
                                perm_a % (uint64_t)key_space, perm_c % (uint64_t)key_space, (hipStream_t)stream));
     return DML_OK;
