@@ -335,7 +335,26 @@ int dml_store_assign_dense_i32_device(dml_store* s, const void* dev_src, int64_t
  * sqrt(delta)) clamped to minAlpha where delta ends above 1, maxDelta updated
  * (FloatMatrixStoreAdaGrad.java:262-277 for the summed update; ties of maxDelta
  * go to the first element in row-major order). Within 1e-6 of the sequential
- * reference, not bit-exact: the exact path is dml_group_push_exchange. */
+ * reference, not bit-exact: the exact path is dml_group_push_exchange.
+ * Arithmetic, as tests/moments_expect.py models it bit for bit: one fp32 add
+ * each for data and delta; alpha = (float)((double)initialAlpha / ((double)factor
+ * * sqrt((double)delta))) where the new delta is above 1; an element whose delta
+ * rose strictly is a maxDelta candidate, the best one (largest delta, then lowest
+ * row-major position) replaces the running record when strictly above it.
+ * Known divergences from the reference:
+ *  1. maxDelta ties: the first element in row-major order, not the first in push /
+ *     record order (FloatMatrixStoreAdaGrad.java:273-277).
+ *  2. NaN / Inf: an element whose delta ends NaN keeps its alpha and is no
+ *     candidate; Inf gives minAlpha.
+ *  3. setAlpha: dev_src carries no mark of the rows a push listed, so alpha is
+ *     rewritten at every element whose delta ends above 1. The reference rewrites
+ *     it only on elements of rows a push lists (:268-272): after
+ *     dml_store_set_alpha with a new initialAlpha, a row with delta above 1 that
+ *     this call's pushes do not list keeps initialAlpha there and gets f(delta)
+ *     here (dml_store_assign_adagrad_device handles the same case with touched
+ *     marks). Likewise an unlisted row's -0.0 data becomes +0.0 (-0.0 + +0.0).
+ * dml_group_push_exchange and dml_group_push_chained are the paths without
+ * these. */
 int dml_store_apply_adagrad_moments_device(dml_store* s, const void* dev_src, int64_t rows);
 
 /* Ordered reduce of n device-resident full-range buckets into a dense device
@@ -559,8 +578,15 @@ int dml_group_push_exchange(dml_group* g, const void* const* dev_bufs, const int
  * x 2 x the model, whatever n is (the exchange path moves n pushes). Within
  * 1e-6, not bit-exact; errors surface at the next call or the flush. Known
  * divergences: a maxDelta tie goes to the first element in row-major order (the
- * reference's: the first in push / record order, FloatMatrixStoreAdaGrad.java:273-277),
- * and with NaN / Inf gradients alpha keeps its value. */
+ * reference's: the first in push / record order, FloatMatrixStoreAdaGrad.java:273-277);
+ * with NaN / Inf gradients alpha keeps its value; and alpha is
+ * rewritten as f(delta) at every element whose delta ends above 1, not only on
+ * rows a push of the call lists: after dml_store_set_alpha, a row with delta
+ * above 1 that no push lists keeps the new initialAlpha in the reference
+ * (:268-272) and gets f(delta) here; such a row's -0.0 data becomes +0.0. The
+ * reduce-scattered message has no per-row touched mark to tell the rows apart.
+ * dml_group_push_exchange and dml_group_push_chained are the paths without
+ * these divergences. */
 int dml_group_push_moments(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n);
 /* Pushes the client already split to this shard (SparseMatrix.java:46-60): the
  * store's exact ordered device push (dml_store_push_batch_device), queued after
