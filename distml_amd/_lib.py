@@ -66,6 +66,8 @@ SIGNATURES = {
     "dml_store_max_delta": (C.c_int, [_vp, _P(C.c_float), _P(_i32), _P(_i32)]),
     "dml_store_fetch": (C.c_int, [_vp, _P(_i64), _i64, _vp, _i64, _P(_i64)]),
     "dml_store_fetch_range": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _P(_i64)]),
+    "dml_store_fetch_device": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _P(_i64), _vp]),
+    "dml_store_fetch_range_device": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _P(_i64), _vp]),
     "dml_store_write_all": (C.c_int, [_vp, _vp, _i64, _P(_i64)]),
     "dml_store_read_all": (C.c_int, [_vp, _vp, _i64]),
     "dml_store_sync_to": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _P(_i64)]),
@@ -142,6 +144,14 @@ DML_E_CAPACITY = 20
 DML_FLAG_FLOAT_ARRAY_REF_STRIDE = 0x1
 DML_FLAG_ASYNC = 0x2
 DML_FLAG_NO_SPECULATION = 0x4
+
+# dml_diag_store_knob
+DML_KNOB_IDENT_FULL_MIN_BYTES = 1
+DML_KNOB_INDEX_CUS = 2
+DML_KNOB_FETCH_KERNEL = 3
+# k_fetch_vec's tile (output bytes per wave instruction / per block)
+DML_FETCH_WAVE_BYTES = 1024
+DML_FETCH_BLOCK_BYTES = 4096
 
 
 class NativeLibraryMissing(RuntimeError):

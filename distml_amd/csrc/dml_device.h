@@ -1,5 +1,5 @@
 // dml_device.h — device-side helpers shared by the kernel files (dml_kernels.hip,
-// dml_sparse.hip): vector load types, wire decode (DataDesc.java:131-192),
+// dml_fetch.hip, dml_sparse.hip): vector load types, wire decode (DataDesc.java:131-192),
 // KeyRange indexOf, IEEE element adds. Not part of the public ABI.
 #pragma once
 #include "dml_internal.h"
@@ -60,6 +60,16 @@ __device__ inline int64_t uni64(int64_t v) {
 }
 __device__ inline uint64_t uni64(uint64_t v) { return (uint64_t)uni64((int64_t)v); }
 constexpr uint32_t kBufOff = 0xFFFFFFF0u;  // an offset past any range: the load reads zeros
+
+// Blocks are dealt to the 8 XCDs round robin (block b on XCD b % 8), each XCD with
+// its own L2. xcd_block() renumbers them so that XCD x runs the x-th contiguous run
+// of block indices, in dispatch order: neighbouring blocks' data meets in one L2.
+// A bijection on [0, gridDim.x) for any grid size.
+__device__ inline int64_t xcd_block() {
+    const int64_t nbk = gridDim.x, b = blockIdx.x, per = (nbk + 7) / 8, x = b % 8, i = b / 8;
+    const int64_t full = nbk - (per - 1) * 8;  // XCDs 0..full-1 hold `per` blocks, the others per - 1
+    return x < full ? x * per + i : full * per + (x - full) * (per - 1) + i;
+}
 
 __device__ inline uint32_t ld32(const uint8_t* p) { return ldg32(p); }
 __device__ inline int64_t ld_key(const uint8_t* p, int K) {

@@ -248,6 +248,27 @@ hipError_t launch_apply_dense_i32chk(int32_t* shard, const int32_t* src, int64_t
 hipError_t launch_fetch(int vtype, const void* shard, const float* alpha, int32_t cols, const int64_t* keys,
                         int64_t key_lo, int64_t n, int64_t first, uint8_t* out, int64_t rec, int K, int value_slot,
                         hipStream_t st);
+// k_fetch with the device key check of dml_store_fetch_device's list form (knob 1).
+hipError_t launch_fetch_checked(int vtype, const void* shard, const float* alpha, int32_t cols, const int64_t* keys,
+                                int64_t n, int64_t first, int64_t last, uint8_t* out, int64_t rec, int K,
+                                int value_slot, unsigned long long* bad, hipStream_t st);
+// k_fetch_vec (dml_fetch.hip): the same records as one stream of whole 16-byte stores.
+// `variant` (diagnostic, bits kFetchVar*) picks the launch shapes DESIGN.md §4.10 compares.
+constexpr int kFetchVarLoadMask = 3;  // 0: by record length, 1: every dword singly, 2: 16-byte shard loads
+constexpr int kFetchVarGather = 1, kFetchVarVload = 2;
+constexpr int kFetchVarXcd = 4;       // blocks renumbered by xcd_block() instead of dispatch order
+constexpr int kFetchVarU1 = 8;        // one vector per thread (4-KiB blocks) ...
+constexpr int kFetchVarU4 = 16;       // ... or four (16-KiB blocks); neither: the shipped choice
+constexpr int kFetchVariants = 24;
+struct FetchVerdict {                // first key outside the shard of the list fetches so far
+    unsigned long long idx;          // its list index, kNoPos: none
+    int64_t key;
+};
+hipError_t launch_fetch_vec(int vtype, const void* shard, const float* alpha, int32_t cols, const int64_t* keys,
+                            int64_t key_lo, int64_t n, int64_t first, int64_t last, uint8_t* out, int64_t rec, int K,
+                            int value_slot, unsigned long long* bad, int variant, hipStream_t st);
+// Behind a list fetch: *bad (this fetch's lowest bad index) into the sticky verdict, *bad reset.
+hipError_t launch_fetch_verdict(unsigned long long* bad, const int64_t* keys, FetchVerdict* v, hipStream_t st);
 hipError_t launch_bswap(int V, const void* src, void* dst, int64_t n, hipStream_t st);
 hipError_t launch_synth_dense(uint8_t* out, int K, int vtype, int64_t first, int64_t shard_rows, int64_t nrec,
                               int32_t cols, uint64_t s0, uint64_t pa, uint64_t pc, hipStream_t st);

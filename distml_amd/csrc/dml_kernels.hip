@@ -602,16 +602,6 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
 }
 
 // ---------------------------------------------------------------------------
-// Blocks are dealt to the 8 XCDs round robin (block b on XCD b % 8), each XCD with
-// its own L2. xcd_block() renumbers them so that XCD x runs the x-th contiguous run
-// of block indices, in dispatch order: neighbouring blocks' data meets in one L2.
-// A bijection on [0, gridDim.x) for any grid size.
-__device__ inline int64_t xcd_block() {
-    const int64_t nbk = gridDim.x, b = blockIdx.x, per = (nbk + 7) / 8, x = b % 8, i = b / 8;
-    const int64_t full = nbk - (per - 1) * 8;  // XCDs 0..full-1 hold `per` blocks, the others per - 1
-    return x < full ? x * per + i : full * per + (x - full) * (per - 1) + i;
-}
-
 // k_reduce_rows: the plain-sum shapes (kAdd, kAddCheckI32, kPreReduce) with
 // RPW neighbouring rows per wave. One push at a time: the wave scalar-loads the
 // push's base / index and its RPW slots, issues RPW x CPW 16-B nt loads (16 for
@@ -2386,16 +2376,25 @@ hipError_t launch_apply_dense(int vtype, void* shard, const void* src, int64_t n
 // record (4/8; 8 for AdaGrad value+alpha and FloatArrayStore's 8-byte slot).
 __device__ inline void st32(uint8_t* p, uint32_t v) { *(uint32_t*)p = v; }
 
-template <typename T>
+// CHECK (dml_store_fetch_device's list form, whose keys no host loop has seen): a key outside
+// [first, last] reads nothing and writes nothing; the lowest list index of one lands in *bad.
+template <typename T, bool CHECK = false>
 __global__ void k_fetch(const T* __restrict__ shard, const float* __restrict__ alpha, int32_t cols,
                         const int64_t* __restrict__ keys, int64_t key_lo, int64_t n, int64_t first,
-                        uint8_t* __restrict__ out, int64_t rec, int K, int value_slot) {
+                        uint8_t* __restrict__ out, int64_t rec, int K, int value_slot, int64_t last = 0,
+                        unsigned long long* __restrict__ bad = nullptr) {
     const int64_t total = n * (int64_t)cols;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t j = t / cols;
         const int32_t c = (int32_t)(t - j * cols);
         const int64_t key = keys ? keys[j] : key_lo + j;
         const int64_t idx = key - first;
+        if constexpr (CHECK) {
+            if (key < first || key > last) {
+                if (c == 0) atomicMin(bad, (unsigned long long)j);
+                continue;
+            }
+        }
         uint8_t* o = out + j * rec;
         if (c == 0) {
             st32(o, (uint32_t)key);
@@ -2422,6 +2421,17 @@ hipError_t launch_fetch(int vtype, const void* shard, const float* alpha, int32_
     if (vtype == kF32) hipLaunchKernelGGL(k_fetch<float>, g, dim3(256), 0, st, (const float*)shard, alpha, cols, keys, key_lo, n, first, out, rec, K, value_slot);
     else if (vtype == kI32) hipLaunchKernelGGL(k_fetch<int32_t>, g, dim3(256), 0, st, (const int32_t*)shard, alpha, cols, keys, key_lo, n, first, out, rec, K, value_slot);
     else hipLaunchKernelGGL(k_fetch<double>, g, dim3(256), 0, st, (const double*)shard, alpha, cols, keys, key_lo, n, first, out, rec, K, value_slot);
+    return hipGetLastError();
+}
+hipError_t launch_fetch_checked(int vtype, const void* shard, const float* alpha, int32_t cols, const int64_t* keys,
+                                int64_t n, int64_t first, int64_t last, uint8_t* out, int64_t rec, int K,
+                                int value_slot, unsigned long long* bad, hipStream_t st) {
+    const int64_t total = n * (int64_t)cols;
+    if (total <= 0) return hipSuccess;
+    const dim3 g(grid_for(total));
+    if (vtype == kF32) hipLaunchKernelGGL((k_fetch<float, true>), g, dim3(256), 0, st, (const float*)shard, alpha, cols, keys, (int64_t)0, n, first, out, rec, K, value_slot, last, bad);
+    else if (vtype == kI32) hipLaunchKernelGGL((k_fetch<int32_t, true>), g, dim3(256), 0, st, (const int32_t*)shard, alpha, cols, keys, (int64_t)0, n, first, out, rec, K, value_slot, last, bad);
+    else hipLaunchKernelGGL((k_fetch<double, true>), g, dim3(256), 0, st, (const double*)shard, alpha, cols, keys, (int64_t)0, n, first, out, rec, K, value_slot, last, bad);
     return hipGetLastError();
 }
 

@@ -249,6 +249,14 @@ struct dml_store {
     ChainI32Rec* crec_host = nullptr;  // pinned copy, DMA'd behind every commit
     hipEvent_t crec_ev = nullptr;
     bool crec_pending = false;
+    // device fetches (dml_store_fetch_device): the list form's key verdict, and the event
+    // behind every device fetch that the caller's stream waits for
+    int64_t fetch_kernel = 0;                 // DML_KNOB_FETCH_KERNEL
+    unsigned long long* fbad_dev = nullptr;   // lowest bad list index of the running fetch
+    FetchVerdict* fver_dev = nullptr;         // sticky: the first bad key of the fetches so far
+    FetchVerdict* fver_host = nullptr;        // pinned copy, DMA'd behind every list fetch
+    hipEvent_t fetch_ev = nullptr;
+    bool fver_pending = false;
     // timing of the dominant kernel
     const char* kname = nullptr;  // its instantiation, as last launched (dml_store_kernel_name)
     bool timing = false;
@@ -1003,9 +1011,35 @@ int ensure_chain_record(dml_store* s) {
     return DML_OK;
 }
 
+// Verdict of the device list fetches (dml_store_fetch_device): the first key outside the
+// shard becomes the store's ArrayIndexOutOfBoundsException, as the host fetch's does.
+// The device record is reopened behind the fetches launched so far once it is reported.
+int collect_fetch_check(dml_store* s, bool block) {
+    if (!s->fver_pending) return DML_OK;
+    if (!block && hipEventQuery(s->fetch_ev) == hipErrorNotReady) return DML_OK;
+    HIPCHK(hipEventSynchronize(s->fetch_ev));
+    s->fver_pending = false;
+    const FetchVerdict v = *s->fver_host;
+    if (v.idx == kNoPos) return DML_OK;
+    HIPCHK(hipMemsetAsync(s->fver_dev, 0xFF, sizeof(FetchVerdict), s->stream));
+    return record_error(s, DML_E_KEY_OUT_OF_SHARD, v.key, -1);
+}
+
+int ensure_fetch_record(dml_store* s) {
+    if (!s->fetch_ev) HIPCHK(hipEventCreateWithFlags(&s->fetch_ev, hipEventDisableTiming));
+    if (s->fver_dev) return DML_OK;
+    HIPCHK(hipMalloc((void**)&s->fbad_dev, sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(s->fbad_dev, 0xFF, sizeof(unsigned long long), s->stream));
+    HIPCHK(hipMalloc((void**)&s->fver_dev, sizeof(FetchVerdict)));
+    HIPCHK(hipMemsetAsync(s->fver_dev, 0xFF, sizeof(FetchVerdict), s->stream));
+    HIPCHK(hipHostMalloc((void**)&s->fver_host, sizeof(FetchVerdict), hipHostMallocDefault));
+    return DML_OK;
+}
+
 int collect_apply_check(dml_store* s, bool block) {
     // a chained int32 commit that brought a closed record home (finished, or waited for)
     if (int rc = collect_chain_check(s, block)) return rc;
+    if (int rc = collect_fetch_check(s, block)) return rc;
     if (!s->neg_pending) return DML_OK;
     if (!block && hipEventQuery(s->neg_ev) == hipErrorNotReady) return DML_OK;
     HIPCHK(hipEventSynchronize(s->neg_ev));
@@ -1226,6 +1260,10 @@ void dml_store_destroy(dml_store* s) {
         if (s->crec_ev) (void)hipEventDestroy(s->crec_ev);
         if (s->neg_host) (void)hipHostFree(s->neg_host);
         if (s->neg_ev) (void)hipEventDestroy(s->neg_ev);
+        (void)hipFree(s->fbad_dev);
+        (void)hipFree(s->fver_dev);
+        if (s->fver_host) (void)hipHostFree(s->fver_host);
+        if (s->fetch_ev) (void)hipEventDestroy(s->fetch_ev);
         (void)hipFree(s->dstage);
         if (s->hstage) (void)hipHostFree(s->hstage);
         (void)hipFree(s->dscr);
@@ -1377,6 +1415,13 @@ void dml_store_clear_error(dml_store* s) {
         (void)hipStreamSynchronize(s->stream);
         s->neg_pending = false;
         (void)hipMemsetAsync(s->neg_dev, 0xFF, sizeof(unsigned long long), s->stream);
+        (void)hipStreamSynchronize(s->stream);
+    }
+    if (s->fver_dev) {  // device list fetches: the verdict is open again
+        DeviceGuard g(s->device);
+        (void)hipStreamSynchronize(s->stream);
+        s->fver_pending = false;
+        (void)hipMemsetAsync(s->fver_dev, 0xFF, sizeof(FetchVerdict), s->stream);
         (void)hipStreamSynchronize(s->stream);
     }
 }
@@ -1554,6 +1599,90 @@ int dml_store_fetch_range(dml_store* s, int64_t first_key, int64_t last_key, uin
     return fetch_impl(s, nullptr, lo <= hi ? hi - lo + 1 : 0, lo, out, cap, out_len);
 }
 
+// Record layout of handleFetch (dense column): bytes per record, and per column in it.
+static int64_t fetch_record_bytes(const dml_store* s, int* value_slot) {
+    if (s->is_matrix) {
+        *value_slot = s->adagrad ? 8 : s->V;
+        return s->K + (int64_t)s->cols * *value_slot;
+    }
+    *value_slot = (s->desc.value_type == DML_ELEMENT_TYPE_FLOAT) ? 8 : s->V;  // FloatArrayStore VALUE_SIZE 8
+    return s->K + *value_slot;
+}
+
+// The device fetch behind its entry checks (begin_call done: every accepted push retired, so
+// s->data names the shard buffer the last of them wrote). dkeys == nullptr: the range form.
+// The encode, the list form's verdict and the event go on the apply stream; the kernels of
+// later pushes queue behind them there.
+static int fetch_device_impl(dml_store* s, const int64_t* dkeys, int64_t nkeys, int64_t key_lo, void* dev_out,
+                             int64_t cap, int64_t* out_len, hipStream_t user) {
+    int value_slot;
+    const int64_t rec = fetch_record_bytes(s, &value_slot);
+    if (((uintptr_t)dev_out & 3) != 0) return set_err(DML_E_INVALID_ARG, "fetch output is not 4-byte aligned");
+    if (*out_len > 0 && (!dev_out || cap < *out_len)) return set_err(DML_E_CAPACITY, "fetch output buffer too small");
+    if (nkeys == 0) return DML_OK;
+    const int which = (int)(s->fetch_kernel & 0xFF), variant = (int)(s->fetch_kernel >> 8);
+    if (int rc = ensure_fetch_record(s)) return rc;
+    const float* alpha = s->adagrad ? s->alpha : nullptr;
+    if (which == 1) {
+        if (dkeys)
+            HIPCHK(launch_fetch_checked(vtype_of(s->desc), s->data, alpha, s->cols, dkeys, nkeys, s->first, s->last,
+                                        (uint8_t*)dev_out, rec, s->K, value_slot, s->fbad_dev, s->stream));
+        else
+            HIPCHK(launch_fetch(vtype_of(s->desc), s->data, alpha, s->cols, nullptr, key_lo, nkeys, s->first,
+                                (uint8_t*)dev_out, rec, s->K, value_slot, s->stream));
+    } else {
+        // k_fetch_vec takes every dense-column shape and is the dispatch's choice on all of
+        // them, so value 2 never meets DML_E_UNSUPPORTED today
+        HIPCHK(launch_fetch_vec(vtype_of(s->desc), s->data, alpha, s->cols, dkeys, key_lo, nkeys, s->first, s->last,
+                                (uint8_t*)dev_out, rec, s->K, value_slot, s->fbad_dev, variant, s->stream));
+    }
+    if (dkeys) {
+        HIPCHK(launch_fetch_verdict(s->fbad_dev, dkeys, s->fver_dev, s->stream));
+        HIPCHK(hipMemcpyAsync(s->fver_host, s->fver_dev, sizeof(FetchVerdict), hipMemcpyDeviceToHost, s->stream));
+        s->fver_pending = true;
+    }
+    HIPCHK(hipEventRecord(s->fetch_ev, s->stream));
+    if (user) {
+        HIPCHK(hipStreamWaitEvent(user, s->fetch_ev, 0));
+        return DML_OK;
+    }
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return collect_fetch_check(s, true);
+}
+
+int dml_store_fetch_device(dml_store* s, const int64_t* dev_keys, int64_t nkeys, void* dev_out, int64_t cap,
+                           int64_t* out_len, void* stream) {
+    if (int rc = check_store(s)) return rc;
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceGuard g(s->device);
+    if (int rc = begin_call(s)) return rc;
+    if (!out_len) return set_err(DML_E_INVALID_ARG, "null out_len");
+    if (nkeys < 0) {
+        *out_len = 0;
+        return set_err(DML_E_INVALID_ARG, "negative key count");
+    }
+    int slot;
+    *out_len = nkeys * fetch_record_bytes(s, &slot);
+    if (nkeys > 0 && !dev_keys) return set_err(DML_E_INVALID_ARG, "null keys");
+    if (((uintptr_t)dev_keys & 7) != 0) return set_err(DML_E_INVALID_ARG, "fetch keys are not 8-byte aligned");
+    return fetch_device_impl(s, dev_keys, nkeys, 0, dev_out, cap, out_len, (hipStream_t)stream);
+}
+
+int dml_store_fetch_range_device(dml_store* s, int64_t first_key, int64_t last_key, void* dev_out, int64_t cap,
+                                 int64_t* out_len, void* stream) {
+    if (int rc = check_store(s)) return rc;
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceGuard g(s->device);
+    if (int rc = begin_call(s)) return rc;
+    if (!out_len) return set_err(DML_E_INVALID_ARG, "null out_len");
+    // KeyRange.intersect (KeyRange.java:124-136): clip to the shard, ascending
+    const int64_t lo = std::max(first_key, s->first), hi = std::min(last_key, s->last);
+    const int64_t nkeys = lo <= hi ? hi - lo + 1 : 0;
+    int slot;
+    *out_len = nkeys * fetch_record_bytes(s, &slot);
+    return fetch_device_impl(s, nullptr, nkeys, lo, dev_out, cap, out_len, (hipStream_t)stream);
+}
+
 // Rows [lo, hi] (local indices), big-endian, row-major: DataOutputStream.write{Float,Int,Double}.
 static int write_rows_be(dml_store* s, int64_t lo, int64_t hi, uint8_t* out) {
     if (hi < lo) return DML_OK;
@@ -1709,6 +1838,11 @@ int dml_diag_store_knob(dml_store* s, int32_t knob, int64_t value) {
     switch (knob) {
         case DML_KNOB_IDENT_FULL_MIN_BYTES: s->ident_full_min = value; return DML_OK;
         case DML_KNOB_INDEX_CUS: return set_cu_split(s, (int)(value & 0xFFFF), (int)(value >> 16));
+        case DML_KNOB_FETCH_KERNEL:
+            if ((value & 0xFF) > 2 || (value >> 8) >= kFetchVariants)
+                return set_err(DML_E_INVALID_ARG, "bad fetch kernel choice");
+            s->fetch_kernel = value;
+            return DML_OK;
         default: return set_err(DML_E_INVALID_ARG, "unknown knob");
     }
 }

@@ -294,6 +294,35 @@ class DataStore:
                                                 C.byref(out_len)), self)
         return out_len.value
 
+    def handleFetchDevice(self, format: DataDesc, rows, out_ptr: int, cap: int, stream: Optional[int] = None) -> int:
+        """handleFetch encoded straight into device memory (dml_store_fetch_device /
+        _fetch_range_device): the bytes handleFetch returns, written at `out_ptr` (on this
+        store's device, 4-byte aligned, `cap` bytes); returns the byte count.
+
+        `rows` is a KeyRange (intersected with localRows as handleFetch does) or a
+        DeviceKeys (int64 keys on this store's device, every one inside the shard).
+        `stream` is a raw hipStream_t (torch.cuda.Stream.cuda_stream): the call returns
+        at once and that stream waits for the encode; a key outside the shard then
+        raises ArrayIndexOutOfBoundsException from flush() or a later call, after the
+        records of the good keys were written. None: synchronous, and the call raises."""
+        self._check_format(format)
+        L = _lib.load()
+        out_len = C.c_int64()
+        st = C.c_void_p(stream or None)
+        if isinstance(rows, DeviceKeys):
+            rc = L.dml_store_fetch_device(self._h, C.c_void_p(rows.ptr or None), rows.n, C.c_void_p(out_ptr or None),
+                                          int(cap), C.byref(out_len), st)
+        elif isinstance(rows, KeyRange):
+            # KeyRange.intersect (KeyRange.java:124-136); an empty one fetches nothing
+            keys = self.localRows.intersect(rows)
+            first, last = (keys.firstKey, keys.lastKey) if isinstance(keys, KeyRange) and keys.size() > 0 else (1, 0)
+            rc = L.dml_store_fetch_range_device(self._h, first, last, C.c_void_p(out_ptr or None), int(cap),
+                                                C.byref(out_len), st)
+        else:
+            raise TypeError("handleFetchDevice takes a KeyRange or DeviceKeys; host keys (KeyList) go to handleFetch")
+        check(rc, self)
+        return out_len.value
+
     def writeAll(self, os=None) -> bytes:
         """Big-endian row-major dump (FloatMatrixStore.java:74-81); writes to `os` if given."""
         n = self._rows * self._cols * np.dtype(self.dtype).itemsize
@@ -451,6 +480,14 @@ class DeviceBatch:
         self.n = len(dev_ptrs)
         self.ptrs = (C.c_void_p * max(self.n, 1))(*dev_ptrs)
         self.lens = (C.c_int64 * max(self.n, 1))(*lens)
+
+
+class DeviceKeys:
+    """`n` int64 keys in device memory at `ptr` (8-byte aligned, on the store's device):
+    the key list of DataStore.handleFetchDevice."""
+
+    def __init__(self, ptr: int, n: int):
+        self.ptr, self.n = int(ptr), int(n)
 
 
 class DMatrix:

@@ -232,6 +232,64 @@ int dml_store_fetch(dml_store* s, const int64_t* keys, int64_t nkeys,
 int dml_store_fetch_range(dml_store* s, int64_t first_key, int64_t last_key,
                           uint8_t* out, int64_t cap, int64_t* out_len);
 
+/* == handleFetch for a worker whose buffers are in HBM (no reference counterpart: the
+ * JVM's fetch returns a byte[]). The same bytes as dml_store_fetch / _fetch_range —
+ * the dense-column layouts of all seven stores: matrices [K-byte key LE][cols x value LE]
+ * (FloatMatrixStore.java:113-174, IntMatrixStore.java:81-140, DoubleMatrixStore.java:80-139),
+ * AdaGrad [value][alpha] pairs in 8-byte slots (FloatMatrixStoreAdaGrad.java:146-213),
+ * arrays [key][value] with FloatArrayStore's 8-byte slot and zero pad
+ * (FloatArrayStore.java:88-108, IntArrayStore.java:78-95, DoubleArrayStore.java:93-113)
+ * — encoded straight into device memory on the store's device, from int64 keys that
+ * are in device memory too (_device) or for the keys of a KeyRange (_range_device,
+ * clipped to the shard by KeyRange.intersect, KeyRange.java:124-136, as
+ * dml_store_fetch_range clips; the range form reads no key array). For a plain store a
+ * fetched record is byte for byte a push record, so the output can be handed to
+ * dml_store_push_batch_device of another store of the same shape (standby, re-shard).
+ *
+ * Entry: like every read, the call first retires every accepted push and returns a
+ * deferred error exactly as dml_store_fetch would.
+ *
+ * Arguments: *out_len = nkeys x record bytes is set on the host first (0 for an empty
+ * intersection, which returns DML_OK with nothing launched, and for nkeys < 0).
+ * DML_E_INVALID_ARG, with nothing launched and no store state changed: a null out_len,
+ * nkeys < 0, a null dev_keys with nkeys > 0, dev_keys not 8-byte aligned, dev_out not
+ * 4-byte aligned. DML_E_CAPACITY: cap < *out_len, or a null dev_out with *out_len > 0.
+ * dev_out needs the alignment of a device push and nothing more (4 bytes), and only
+ * [dev_out, dev_out + *out_len) is ever written, so a fetch can be written straight
+ * into a packed send buffer, between other live data.
+ *
+ * Ordering: the encode is enqueued on the store's apply stream (dml_store_stream).
+ * With a non-null `stream` (a hipStream_t of the store's device) the call does not
+ * wait for it: it records an event behind the encode and makes `stream` wait for that
+ * event, and the caller orders its own work on `stream`. stream == NULL makes the call
+ * synchronous: it returns after the bytes are written. dev_keys and dev_out must stay
+ * valid until then. Kernels of later pushes queue behind the fetch on the apply
+ * stream, so a fetch sees every push accepted before it and none accepted after it,
+ * with no flush in between (DESIGN.md §4.10 says why that holds for the second shard
+ * buffer of speculative chunks).
+ *
+ * Keys are checked on the device, by range as 64-bit values (first <= key <= last) as
+ * dml_store_fetch checks them. For a key outside the shard nothing is read from the
+ * shard and no byte of that key's record is written; the lowest list index of such a
+ * key is kept and comes home through a pinned word behind the encode. stream == NULL:
+ * the call itself returns DML_E_KEY_OUT_OF_SHARD. Otherwise the flush, or the next
+ * call into the store that finds the encode finished (a push does not wait for it; a
+ * read does), returns it. Either way the store's error state holds that key and col -1,
+ * sticky until dml_store_clear_error, as after the host fetch. The one difference from
+ * the host call: dml_store_fetch refuses before anything is copied, while this call
+ * has already written the records of the good keys.
+ *
+ * A group rank uses these calls on its dml_group_store handle after dml_group_flush,
+ * like every other read of that handle. */
+int dml_store_fetch_device(dml_store* s, const int64_t* dev_keys, int64_t nkeys,
+                           void* dev_out, int64_t cap, int64_t* out_len, void* stream);
+int dml_store_fetch_range_device(dml_store* s, int64_t first_key, int64_t last_key,
+                                 void* dev_out, int64_t cap, int64_t* out_len, void* stream);
+/* Output bytes of one wave instruction's 64 vectors and of one block's tile in the
+ * device fetch's encode kernel (k_fetch_vec): the sizes its tests place stream ends at. */
+#define DML_FETCH_WAVE_BYTES 1024
+#define DML_FETCH_BLOCK_BYTES 4096
+
 /* writeAll/readAll (FloatMatrixStore.java:74-91 etc.): big-endian row-major
  * values, the bytes DataOutputStream.writeFloat/writeInt/writeDouble emit.
  * read_all assigns the elements the stream holds before failing with
@@ -741,6 +799,15 @@ int dml_diag_ring_rs(int32_t value_type, const void* dev_partial, void* dev_recv
  * default) both on every CU; pattern 0 spreads the k CUs evenly over the CU numbering,
  * 1 takes the first k (config 3: the partition beside the leaf). */
 #define DML_KNOB_INDEX_CUS 2
+/* DML_KNOB_FETCH_KERNEL: the encode kernel of dml_store_fetch_device / _fetch_range_device.
+ * 0 (the default) = the library's dispatch; 1 = always k_fetch (the host fetch's kernel, one
+ * thread per key and column); 2 = always k_fetch_vec (whole 16-byte stores), where the
+ * fetch returns DML_E_UNSUPPORTED if that kernel cannot take the store's shape (today it
+ * takes every dense-column shape). With 2, bits 8-12 pick one of the launch shapes
+ * DESIGN.md §4.10 compares (bits 8-9: 0 = shard loads chosen by record length, 1 = every
+ * dword gathered singly, 2 = 16-byte loads; 1024: blocks renumbered XCD-contiguous;
+ * 2048 / 4096: one / four vectors per thread); the bytes are the same for every value. */
+#define DML_KNOB_FETCH_KERNEL 3
 int dml_diag_store_knob(dml_store* s, int32_t knob, int64_t value);
 
 /* --- misc --------------------------------------------------------------- */
