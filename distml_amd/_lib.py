@@ -112,6 +112,9 @@ SIGNATURES = {
     "dml_group_push_local": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
     "dml_group_push_chained": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
     "dml_group_push_chained_i32": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
+    "dml_group_pull": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _P(_i64), _P(_i64), _vp]),
+    "dml_diag_pull_kernels": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _P(_i64), _vp, _vp, _i64, _i32, _vp,
+                                        _P(C.c_float), _P(C.c_float)]),
     "dml_group_debug_fail_verify": (C.c_int, [_vp, _i32]),
     "dml_group_flush": (C.c_int, [_vp]),
     "dml_group_destroy": (None, [_vp]),
@@ -152,6 +155,11 @@ DML_KNOB_FETCH_KERNEL = 3
 # k_fetch_vec's tile (output bytes per wave instruction / per block)
 DML_FETCH_WAVE_BYTES = 1024
 DML_FETCH_BLOCK_BYTES = 4096
+# dml_group_pull: the flag, and k_pull_unsplit's tile
+DML_PULL_REQUEST_ORDER = 0x1
+DML_PULL_MAX_WORLD = 64
+DML_PULL_WAVE_BYTES = 1024
+DML_PULL_BLOCK_BYTES = 4096
 
 
 class NativeLibraryMissing(RuntimeError):

@@ -27,6 +27,10 @@
 // for all three kinds of slice; what a kind carries and checks is described at ChainKind. One
 // documented divergence (AdaGrad: the alpha of an element whose delta comes home NaN,
 // DESIGN.md §2); dml_group_push_exchange is the path without it.
+// dml_group_pull is the fetch half (WorkerAgent.fetch, WorkerAgent.java:74-122): a collective call
+// in which every rank's device key list is split by owner, owners encode the handleFetch records
+// on their store's stream behind every earlier call, and counts, keys and records travel as
+// grouped ncclSend / ncclRecv.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -120,6 +124,18 @@ struct dml_group {
     // int32 chain: a commit's verdict record is on its way to the host; a non-chained
     // call behind it waits for it first (the reference refuses pushes to a closed store)
     bool cverdict = false;
+    // collective pull (dml_group_pull), allocated on its first call and grown on demand: the
+    // partition's workspace, [keys by owner | perm], the keys the peers ask this shard for,
+    // their records (sent), the records received (request-order mode only)
+    void* pws = nullptr;
+    void* pkeys = nullptr;
+    void* prkeys = nullptr;
+    void* psend = nullptr;
+    void* precv = nullptr;
+    int64_t pws_cap = 0, pkeys_cap = 0, prkeys_cap = 0, psend_cap = 0, precv_cap = 0;
+    int64_t* pcnt = nullptr;     // device: [the partition's totals world + 1][asked of q world][asked by q world]
+    hipEvent_t pstep = nullptr;  // from one of the pull's streams to the next
+    hipEvent_t pdone = nullptr;  // the last pull's last kernel or transfer: one pull is in flight
 };
 
 namespace {
@@ -244,6 +260,10 @@ void group_free(dml_group* g) {
         if (g->mapplied[i]) (void)hipEventDestroy(g->mapplied[i]);
     }
     if (g->xcnt) (void)hipFree(g->xcnt);
+    for (void* b : {g->pws, g->pkeys, g->prkeys, g->psend, g->precv, (void*)g->pcnt})
+        if (b) (void)hipFree(b);
+    for (hipEvent_t e : {g->pstep, g->pdone})
+        if (e) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) {
         if (g->xsend[i]) (void)hipFree(g->xsend[i]);
         if (g->xrecv[i]) (void)hipFree(g->xrecv[i]);
@@ -967,6 +987,159 @@ int dml_group_push_chained_i32(dml_group* g, const void* const* dev_bufs, const 
                                "dml_group_push_chained)"
                              : nullptr,
                       dev_bufs, lens, n);
+}
+
+// The collective group pull (contract: include/distml_ps.h; protocol and ordering argument:
+// DESIGN.md §6). WorkerAgent.fetch (WorkerAgent.java:74-122) for key lists in HBM: partition
+// the list by owner (cstream), exchange counts and keys (rstream), every owner encodes what it
+// was asked for with the store's own k_fetch_vec (the store's stream, behind every earlier
+// push), the records come back (rstream) — straight into dev_out in owner-major order, or into
+// a receive buffer that k_pull_unsplit permutes into request order.
+// A rank that fails locally (bad argument, short cap, a deferred store error) asks for nothing
+// or reports late, but makes every send and receive: no peer waits for it. A HIP,
+// RCCL or allocation failure in the middle of the protocol is not covered: it returns at once,
+// as in dml_group_push_exchange.
+int dml_group_pull(dml_group* g, const int64_t* dev_keys, int64_t nkeys, void* dev_out, int64_t cap, int32_t flags,
+                   int64_t* out_len, int64_t* out_counts, void* stream) {
+    if (!g) return set_error(DML_E_INVALID_ARG, "null group");
+    // the same answer on every rank, before any send and before anything is written: nobody waits
+    // for a peer (the partition kernels keep one LDS entry per owner)
+    if (g->world > DML_PULL_MAX_WORLD)
+        return set_error(DML_E_UNSUPPORTED, "dml_group_pull serves groups of at most 64 ranks");
+    HIPCHK(hipSetDevice(g->device));
+    const int W = g->world, me = g->rank;
+    const bool reqorder = (flags & DML_PULL_REQUEST_ORDER) != 0;
+    int local = DML_OK;
+    if (!out_len || nkeys < 0 || (nkeys > 0 && !dev_keys) || (flags & ~DML_PULL_REQUEST_ORDER))
+        local = set_error(DML_E_INVALID_ARG, "bad pull arguments");
+    else if (((uintptr_t)dev_keys & 7u) || ((uintptr_t)dev_out & 3u))
+        local = set_error(DML_E_INVALID_ARG, "pull keys are 8-byte aligned, the output 4-byte aligned");
+    if (out_len) *out_len = 0;
+    for (int q = 0; q < W && out_counts; ++q) out_counts[q] = 0;
+    if (!g->pdone) {
+        HIPCHK(hipMalloc((void**)&g->pcnt, sizeof(int64_t) * (size_t)(3 * W + 1)));
+        HIPCHK(hipEventCreateWithFlags(&g->pstep, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&g->pdone, hipEventDisableTiming));
+    }
+    HIPCHK(hipEventSynchronize(g->pdone));  // the previous pull is done with the buffers below
+    // what dml_group_flush drains: the applies and commits of every earlier call are on the
+    // store's stream after this, except a held exchange's slices (handed over below)
+    int prior = DML_OK;
+    auto note = [&](int rc) {
+        if (rc != DML_OK && prior == DML_OK) prior = rc;
+    };
+    note(end_pending(g, 0));
+    note(end_moments(g, 0));
+    note(end_chained(g, 0));
+    note(chain_i32_verdict(g));
+    int64_t rec = 0;
+    GRC(store_fetch_record_bytes(g->store, &rec));
+
+    // the partition: keys by owner, the counts on the host (the call's first host wait)
+    const int64_t n = local == DML_OK ? nkeys : 0;
+    std::vector<int64_t> cnt((size_t)W + 1, 0);
+    int64_t* pkeys = nullptr;
+    int64_t* perm = nullptr;
+    if (n > 0) {
+        int rc = grow(&g->pws, &g->pws_cap, (int64_t)pull_partition_ws_bytes(n, W));
+        if (rc == DML_OK) rc = grow(&g->pkeys, &g->pkeys_cap, 16 * n);
+        if (rc == DML_OK) {
+            pkeys = (int64_t*)g->pkeys;
+            perm = reqorder ? pkeys + n : nullptr;
+            HIPCHK(launch_pull_partition(dev_keys, n, g->total_rows, g->step_rows, W, (uint8_t*)g->pws, pkeys, nullptr,
+                                         nullptr, perm, g->pcnt, g->cstream));
+            HIPCHK(hipMemcpyAsync(cnt.data(), g->pcnt, sizeof(int64_t) * cnt.size(), hipMemcpyDeviceToHost, g->cstream));
+            HIPCHK(hipStreamSynchronize(g->cstream));
+        }
+        if (rc != DML_OK) local = rc;
+    }
+    int64_t kept = 0;
+    for (int q = 0; q < W; ++q) kept += cnt[(size_t)q];
+    if (local == DML_OK) {
+        *out_len = kept * rec;
+        for (int q = 0; q < W && out_counts; ++q) out_counts[q] = cnt[(size_t)q];
+        if (kept * rec > cap || (kept > 0 && !dev_out)) local = set_error(DML_E_CAPACITY, "pull output buffer too small");
+    }
+    if (local != DML_OK) {  // the rank asks for nothing
+        std::fill(cnt.begin(), cnt.end(), 0);
+        kept = 0;
+    }
+    std::vector<int64_t> koff((size_t)W + 1, 0);  // owner q's keys / records start at koff[q]
+    for (int q = 0; q < W; ++q) koff[(size_t)q + 1] = koff[(size_t)q] + cnt[(size_t)q];
+    uint8_t* const out = (uint8_t*)dev_out;
+    hipStream_t last = g->sstream;
+    int enc = DML_OK;
+
+    if (W == 1) {
+        if (g->xheld) {
+            HIPCHK(hipStreamSynchronize(g->rstream));
+            note(hand_over(g));
+        }
+        enc = store_pull_encode(g->store, pkeys, kept, out);
+    } else {
+        // counts: what this rank asks of q goes out, what q asks of this shard comes in
+        std::vector<int64_t> theirs((size_t)W, 0);
+        int64_t* const dmine = g->pcnt + W + 1;
+        int64_t* const dtheirs = dmine + W;
+        HIPCHK(hipMemcpyAsync(dmine, cnt.data(), sizeof(int64_t) * (size_t)W, hipMemcpyHostToDevice, g->rstream));
+        GNCCL(ncclGroupStart());
+        for (int q = 0; q < W; ++q) {
+            if (q == me) continue;
+            GNCCL(ncclSend(dmine + q, 1, ncclInt64, q, g->comm, g->rstream));
+            GNCCL(ncclRecv(dtheirs + q, 1, ncclInt64, q, g->comm, g->rstream));
+        }
+        GNCCL(ncclGroupEnd());
+        HIPCHK(hipMemcpyAsync(theirs.data(), dtheirs, sizeof(int64_t) * (size_t)W, hipMemcpyDeviceToHost, g->rstream));
+        HIPCHK(hipStreamSynchronize(g->rstream));  // also completes the previous exchange call's all-to-all
+        note(hand_over(g));
+        theirs[(size_t)me] = 0;  // the rank's own keys never leave it
+        std::vector<int64_t> roff((size_t)W + 1, 0);
+        for (int q = 0; q < W; ++q) roff[(size_t)q + 1] = roff[(size_t)q] + theirs[(size_t)q];
+        const int64_t nrk = roff[(size_t)W];
+        GRC(grow(&g->prkeys, &g->prkeys_cap, nrk * 8));
+        GRC(grow(&g->psend, &g->psend_cap, nrk * rec));
+        if (reqorder) GRC(grow(&g->precv, &g->precv_cap, kept * rec));
+        int64_t* const rkeys = (int64_t*)g->prkeys;
+        uint8_t* const sp = (uint8_t*)g->psend;
+        uint8_t* const land = reqorder ? (uint8_t*)g->precv : out;  // owner-major either way
+        // every rank issues every send and receive, empty ones included (zero elements: they
+        // name a valid address all the same)
+        auto at = [&](auto* p, int64_t off, int64_t count) { return count > 0 ? (void*)(p + off) : (void*)g->pcnt; };
+        // keys
+        GNCCL(ncclGroupStart());
+        for (int q = 0; q < W; ++q) {
+            if (q == me) continue;
+            const int64_t ns = cnt[(size_t)q], nr = theirs[(size_t)q];
+            GNCCL(ncclSend(at(pkeys, koff[(size_t)q], ns), (size_t)ns, ncclInt64, q, g->comm, g->rstream));
+            GNCCL(ncclRecv(at(rkeys, roff[(size_t)q], nr), (size_t)nr, ncclInt64, q, g->comm, g->rstream));
+        }
+        GNCCL(ncclGroupEnd());
+        HIPCHK(hipEventRecord(g->pstep, g->rstream));
+        // the encodes, on the store's stream behind every earlier call's apply: the rank's own
+        // slice at its owner-major place (it needs no transfer), then one call over the keys of
+        // every peer into the packed send buffer
+        enc = store_pull_encode(g->store, pkeys + koff[(size_t)me], cnt[(size_t)me], land + koff[(size_t)me] * rec);
+        HIPCHK(hipStreamWaitEvent(g->sstream, g->pstep, 0));
+        const int enc2 = store_pull_encode(g->store, rkeys, nrk, sp);
+        if (enc == DML_OK) enc = enc2;
+        HIPCHK(hipEventRecord(g->pstep, g->sstream));
+        HIPCHK(hipStreamWaitEvent(g->rstream, g->pstep, 0));
+        // records
+        GNCCL(ncclGroupStart());
+        for (int q = 0; q < W; ++q) {
+            if (q == me) continue;
+            const int64_t bs = theirs[(size_t)q] * rec, br = cnt[(size_t)q] * rec;
+            GNCCL(ncclSend(at(sp, roff[(size_t)q] * rec, bs), (size_t)bs, ncclUint8, q, g->comm, g->rstream));
+            GNCCL(ncclRecv(at(land, koff[(size_t)q] * rec, br), (size_t)br, ncclUint8, q, g->comm, g->rstream));
+        }
+        GNCCL(ncclGroupEnd());
+        if (reqorder) HIPCHK(launch_pull_unsplit(land, perm, kept, rec, out, 0, g->rstream));
+        last = g->rstream;
+    }
+    HIPCHK(hipEventRecord(g->pdone, last));
+    if (stream) HIPCHK(hipStreamWaitEvent((hipStream_t)stream, g->pdone, 0));
+    else HIPCHK(hipEventSynchronize(g->pdone));
+    return local != DML_OK ? local : prior != DML_OK ? prior : enc;
 }
 
 int dml_group_debug_fail_verify(dml_group* g, int32_t nth) {

@@ -460,5 +460,17 @@ int store_adagrad_ptrs(dml_store* s, float** delta, void** maxdelta);
 // its error state, DML_E_NEGATIVE_COUNTER with the record's key and col.
 int store_chain_i32_record(dml_store* s, void** dev_rec);
 int store_chain_i32_collect(dml_store* s, bool block);
+// The store's side of a group pull (dml_store.hip): the handleFetch record's bytes, and the
+// encode of keys that all lie inside the shard, enqueued on the apply stream whatever the
+// entry's deferred error is (it is returned behind the launch).
+int store_fetch_record_bytes(dml_store* s, int64_t* rec);
+int store_pull_encode(dml_store* s, const int64_t* dev_keys, int64_t nkeys, void* dev_out);
+// dml_pull.hip: the key partition and the record permutation of dml_group_pull.
+size_t pull_partition_ws_bytes(int64_t n, int world);
+hipError_t launch_pull_partition(const int64_t* keys, int64_t n, int64_t total_rows, int64_t step, int world,
+                                 uint8_t* ws, int64_t* out_keys, int64_t* slot, int64_t* kept, int64_t* perm,
+                                 int64_t* tot, hipStream_t st);
+hipError_t launch_pull_unsplit(const void* src, const int64_t* perm, int64_t nrec, int64_t rec_bytes, void* dst,
+                               int variant, hipStream_t st);
 
 }  // namespace dml

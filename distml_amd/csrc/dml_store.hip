@@ -2144,3 +2144,33 @@ int dml_synth_fill_store(dml_store* s, uint64_t seed) {
 }
 
 }  // extern "C"
+
+// The owner's side of dml_group_pull (dml_group.hip): the records of `nkeys` device keys, all
+// inside the shard (the requesters' partition put them there), encoded by k_fetch_vec into
+// dev_out on the apply stream; nothing is waited for. Entry as every read's (begin_call), but
+// what it reports does not stop the encode: the peers have sized their receives, so a shard
+// with a deferred error, or in its sticky error state, answers with its bytes as they stand,
+// and the error is returned behind the launch.
+namespace dml {
+int store_pull_encode(dml_store* s, const int64_t* dev_keys, int64_t nkeys, void* dev_out) {
+    if (int rc = check_store(s)) return rc;
+    std::lock_guard<std::mutex> lk(s->mu);
+    DeviceGuard g(s->device);
+    const int held = begin_call(s);
+    if (nkeys <= 0) return held;
+    int value_slot;
+    const int64_t rec = fetch_record_bytes(s, &value_slot);
+    if (int rc = ensure_fetch_record(s)) return rc;
+    const int variant = (s->fetch_kernel & 0xFF) == 2 ? (int)(s->fetch_kernel >> 8) : 0;
+    HIPCHK(launch_fetch_vec(vtype_of(s->desc), s->data, s->adagrad ? s->alpha : nullptr, s->cols, dev_keys, 0, nkeys,
+                            s->first, s->last, (uint8_t*)dev_out, rec, s->K, value_slot, s->fbad_dev, variant, s->stream));
+    return held;
+}
+
+int store_fetch_record_bytes(dml_store* s, int64_t* rec) {
+    if (int rc = check_store(s)) return rc;
+    int value_slot;
+    *rec = fetch_record_bytes(s, &value_slot);
+    return DML_OK;
+}
+}  // namespace dml

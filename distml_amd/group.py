@@ -790,6 +790,23 @@ class NativeShardGroup:
         ls = (C.c_int64 * max(n, 1))(*lens)
         check(self._L.dml_group_push_exchange(C.c_void_p(self._h), ptrs, ls, n), self.store)
 
+    def pull(self, dev_keys: int, nkeys: int, dev_out: int, cap: int, request_order: bool = False,
+             stream: int = 0):
+        """The collective pull (dml_group_pull): the handleFetch records of `nkeys` int64 keys at
+        device address `dev_keys`, from whichever shards own them, written to device address
+        `dev_out` (4-byte aligned, `cap` bytes): owner-major (the reference's byte[][]
+        concatenated), or, with request_order, record j for the j-th key that lies inside the
+        model. Every rank calls it at the same place among its group calls. It sees every push
+        call made before it, with no flush in between. Returns (out_len, counts): the bytes
+        written and the number of records from every owner. stream = 0 waits for the bytes;
+        otherwise that hipStream_t waits for them."""
+        out_len = C.c_int64(0)
+        counts = (C.c_int64 * self.world)()
+        check(self._L.dml_group_pull(C.c_void_p(self._h), C.c_void_p(dev_keys), nkeys, C.c_void_p(dev_out), cap,
+                                     _lib.DML_PULL_REQUEST_ORDER if request_order else 0, C.byref(out_len), counts,
+                                     C.c_void_p(stream)), self.store)
+        return out_len.value, list(counts)
+
     def flush(self) -> None:
         check(self._L.dml_group_flush(C.c_void_p(self._h)), self.store)
 

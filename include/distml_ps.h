@@ -724,6 +724,62 @@ int dml_group_push_chained(dml_group* g, const void* const* dev_bufs, const int6
  * dense int32 matrix: DML_E_UNSUPPORTED, on every rank alike and before any
  * send. */
 int dml_group_push_chained_i32(dml_group* g, const void* const* dev_bufs, const int64_t* lens, int32_t n);
+/* Collective pull: WorkerAgent.fetch (WorkerAgent.java:74-122) for workers whose key lists
+ * and buffers are in HBM. Every rank calls it at the same position in its sequence of group
+ * calls, each with its own int64 key list in device memory (8-byte aligned; nkeys may differ
+ * per rank and may be 0), and receives the dense-column handleFetch records of its keys from
+ * the shards that own them, byte for byte what dml_store_fetch_device writes on the owner
+ * (every store kind: the K-byte key, AdaGrad's [value][alpha] pairs, FloatArrayStore's padded
+ * slot).
+ *
+ * Split: keys are partitioned by owner under KeyRange.linearSplit(world) of [0, total_rows)
+ * (KeyRange.java:68-80), stably: within one owner the list's order is kept, as
+ * partitions[i].intersect(rowKeys) keeps it (KeyList.java:74-86). A key outside
+ * [0, total_rows) is dropped (tested as a 64-bit value, no narrowing: the client's
+ * intersect, and dml_shard_split); a key listed twice gets two records.
+ *
+ * Output, flags == 0 (owner-major): owner 0's records, then owner 1's, ..., each in list
+ * order: the reference's byte[][] concatenated. out_counts[q] (world entries, may be NULL) =
+ * records from owner q; *out_len = total bytes. DML_PULL_REQUEST_ORDER: record j is the
+ * record of the j-th kept key of the list (no key dropped: record i belongs to keys[i]);
+ * out_counts as before. dev_out is 4-byte aligned and nothing more, and only
+ * [dev_out, dev_out + *out_len) is ever written.
+ *
+ * Visibility: a pull sees every group push call that any rank issued before it, and none
+ * issued after it, with no flush in between: each rank first drains what dml_group_flush
+ * drains (pending full-range, moments and chained handles, the int32 chain's verdict; the
+ * previous dml_group_push_exchange's held slices are handed over after this call's first
+ * stream wait, as dml_group_push_exchange does), then encodes on its store's apply stream.
+ *
+ * `stream` as in dml_store_fetch_device: NULL makes the call synchronous; otherwise
+ * `stream` waits on one event behind the call's last kernel or transfer, and dev_out stays
+ * valid until then. dev_keys must be complete when the call is made (the partition reads
+ * them at once, and the host waits for its counts and for the count exchange; the owner
+ * encode enters the store like every read, so the host may also wait there for earlier
+ * pushes' index and verdict, as in dml_store_fetch_device). One pull is
+ * in flight per group: the next pull first waits for this one's event.
+ *
+ * Local failures never strand a peer: a rank with a bad argument (DML_E_INVALID_ARG: a null
+ * out_len, nkeys < 0, a null or misaligned dev_keys, a misaligned dev_out, an unknown flag)
+ * or whose cap is below the kept records' bytes (DML_E_CAPACITY; *out_len and out_counts say
+ * what was needed) asks for nothing, writes nothing, still serves its shard and takes part
+ * in every exchange, and returns its error afterwards. A rank whose drain returns a deferred
+ * store error, or whose shard is in its sticky error state, serves its shard's bytes as they
+ * stand; the deferred error is returned at the end (a sticky state alone is DML_OK).
+ * That guarantee covers argument, capacity and deferred store errors. A HIP, RCCL or
+ * allocation failure in the middle of the call (DML_E_HIP) returns at once, as in
+ * dml_group_push_exchange: its peers may then wait for it.
+ * At world 1 there is no exchange: the records are encoded straight into dev_out.
+ * A group of more than DML_PULL_MAX_WORLD ranks: DML_E_UNSUPPORTED, on every rank alike,
+ * before any send, with nothing written (out_len and out_counts included). */
+#define DML_PULL_REQUEST_ORDER 0x1
+#define DML_PULL_MAX_WORLD 64
+int dml_group_pull(dml_group* g, const int64_t* dev_keys, int64_t nkeys, void* dev_out, int64_t cap, int32_t flags,
+                   int64_t* out_len, int64_t* out_counts, void* stream);
+/* Output bytes of one wave instruction's 64 lines and of one block's tile in the request-order
+ * permutation kernel (k_pull_unsplit): the sizes its tests place stream ends at. */
+#define DML_PULL_WAVE_BYTES 1024
+#define DML_PULL_BLOCK_BYTES 4096
 int dml_group_flush(dml_group* g);
 void dml_group_destroy(dml_group* g);
 /* Fault injection for tests: the nth full-range call finished from now on (1 = the
@@ -786,6 +842,23 @@ int dml_diag_gather_floor(int32_t* dev_shard, int32_t cols, const int32_t* dev_r
  * reduce-scatter's (no peer contributes): timing only. */
 int dml_diag_ring_rs(int32_t value_type, const void* dev_partial, void* dev_recv, void* dev_landing,
                      int64_t chunk_bytes, int32_t world, int32_t rank, int32_t channels, void* stream);
+
+/* The two kernels of dml_group_pull on the caller's buffers, one GPU, no group (diagnostic,
+ * tests and timing). The partition: nkeys int64 keys (8-byte aligned) split by owner under
+ * linearSplit(world) of [0, total_rows), world <= 64: dev_part_keys (nkeys entries) receives
+ * the kept keys as [owner][list order]; dev_slot / dev_kept (nkeys entries each, may be NULL)
+ * every list index's owner-major slot and kept index (the list index minus the dropped keys
+ * before it), -1 for a dropped key; counts (host, world + 1 entries) the per-owner counts and
+ * the dropped count. The permutation (k_pull_unsplit; skipped when dev_src or dev_dst is
+ * NULL): dev_src holds one record of rec_bytes (whole dwords, >= 8) per kept key in
+ * owner-major order, dev_dst receives them in list order; both 4-byte aligned, only
+ * [dev_dst, dev_dst + kept x rec_bytes) is written. variant: 0 = the shipped load choice,
+ * 1 = every dword gathered singly, 2 = 16-byte loads. Synchronous; *ms_partition /
+ * *ms_unsplit (may be NULL) = kernel times by HIP events on `stream`. */
+int dml_diag_pull_kernels(const int64_t* dev_keys, int64_t nkeys, int64_t total_rows, int32_t world,
+                          int64_t* dev_part_keys, int64_t* dev_slot, int64_t* dev_kept, int64_t* counts,
+                          const void* dev_src, void* dev_dst, int64_t rec_bytes, int32_t variant, void* stream,
+                          float* ms_partition, float* ms_unsplit);
 
 /* Store tuning knob (diagnostic / tests): DML_KNOB_IDENT_FULL_MIN_BYTES = the slot-table
  * size (bytes) from which an AdaGrad chunk of full-range pushes checks every record's key

@@ -14,11 +14,16 @@ public class GpuShardGroup implements AutoCloseable {
     static { System.loadLibrary("distml_jni"); }
 
     private long handle;  // dml_group*
+    private final int world;
+
+    /** dml_group_pull's flag: records in the order of the key list instead of owner-major. */
+    public static final int PULL_REQUEST_ORDER = 1;
 
     public static byte[] uniqueId() { return nativeUniqueId(); }
 
     public GpuShardGroup(byte[] uniqueId, int world, int rank, int device, DataDesc format,
                          long totalRows, int cols, int pieces) {
+        this.world = world;
         handle = nativeGroupCreate(uniqueId, world, rank, device, format.dataType, format.keyType,
                 format.valueType, format.denseRow ? 1 : 0, format.denseColumn ? 1 : 0,
                 format.adaGrad ? 1 : 0, totalRows, cols, pieces);
@@ -69,6 +74,22 @@ public class GpuShardGroup implements AutoCloseable {
      */
     public void pushChainedChecked(long[] devPtrs, long[] lens) { nativeGroupPush(handle, devPtrs, lens, 5); }
 
+    /**
+     * WorkerAgent.fetch (WorkerAgent.java:74-122) for key lists in HBM, a collective call: every
+     * rank passes its own nkeys long keys at device address devKeys and receives their
+     * handleFetch records at devOut (cap bytes) from the shards that own them, owner 0's
+     * first, each in list order (the reference's byte[][] concatenated), or in list order with
+     * PULL_REQUEST_ORDER. Keys outside the model are dropped. It sees every push call made
+     * before it, with no flush() in between. Returns the number of records from every owner.
+     */
+    public long[] pull(long devKeys, long nkeys, long devOut, long cap, int flags) {
+        java.nio.ByteBuffer b = java.nio.ByteBuffer.wrap(nativeGroupPull(handle, devKeys, nkeys, devOut, cap, flags, world))
+                .order(java.nio.ByteOrder.LITTLE_ENDIAN);
+        long[] counts = new long[world];
+        for (int q = 0; q < world; ++q) counts[q] = b.getLong();
+        return counts;
+    }
+
     /** Every call applied; throws the first deferred key / repeated-row error. */
     public void flush() { nativeGroupFlush(handle); }
 
@@ -87,6 +108,8 @@ public class GpuShardGroup implements AutoCloseable {
                                                  int keyType, int valueType, int denseRow, int denseColumn,
                                                  int adaGrad, long totalRows, int cols, int pieces);
     private static native void nativeGroupPush(long g, long[] devPtrs, long[] lens, int mode);
+    private static native byte[] nativeGroupPull(long g, long devKeys, long nkeys, long devOut, long cap, int flags,
+                                                 int world);
     private static native void nativeGroupFlush(long g);
     private static native long nativeGroupStore(long g);
     private static native void nativeGroupDestroy(long g);

@@ -354,6 +354,32 @@ JNIEXPORT void JNICALL GFN(nativeGroupPush)(JNIEnv* env, jclass, jlong g, jlongA
     if (rc) throw_for(env, rc);
 }
 
+// The collective pull (dml_group_pull), synchronous: the records are in devOut on return. The
+// per-owner record counts come back as `world` little-endian int64 in a byte[] (GpuShardGroup
+// decodes them into a long[]).
+JNIEXPORT jbyteArray JNICALL GFN(nativeGroupPull)(JNIEnv* env, jclass, jlong g, jlong dev_keys, jlong nkeys,
+                                                   jlong dev_out, jlong cap, jint flags, jint world) {
+    // the call writes one count per rank of the group and refuses groups past DML_PULL_MAX_WORLD
+    // before it writes any: room for that many whatever `world` the caller passes
+    if (world < 0 || world > DML_PULL_MAX_WORLD) {
+        env->ThrowNew(env->FindClass("java/lang/IllegalArgumentException"), "pull: world must be 0..64");
+        return nullptr;
+    }
+    std::vector<int64_t> counts((size_t)DML_PULL_MAX_WORLD, 0);
+    int64_t len = 0;
+    if (int rc = dml_group_pull(G(g), reinterpret_cast<const int64_t*>(dev_keys), nkeys,
+                                reinterpret_cast<void*>(dev_out), cap, flags, &len, counts.data(), nullptr)) {
+        throw_for(env, rc);
+        return nullptr;
+    }
+    std::vector<jbyte> le((size_t)world * 8);
+    for (jint q = 0; q < world; ++q)
+        for (int b = 0; b < 8; ++b) le[(size_t)q * 8 + b] = (jbyte)((uint64_t)counts[(size_t)q] >> (8 * b));
+    jbyteArray out = env->NewByteArray((jsize)le.size());
+    env->SetByteArrayRegion(out, 0, (jsize)le.size(), le.data());
+    return out;
+}
+
 JNIEXPORT void JNICALL GFN(nativeGroupFlush)(JNIEnv* env, jclass, jlong g) {
     if (int rc = dml_group_flush(G(g))) throw_for(env, rc);
 }
