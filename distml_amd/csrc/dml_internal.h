@@ -393,6 +393,47 @@ hipError_t launch_rand(int vtype, void* p, int64_t rows, int32_t cols, uint64_t 
 hipError_t launch_synth_fill(int vtype, void* p, int64_t n, uint64_t s0, hipStream_t st);
 hipError_t launch_key_rows(const uint8_t* base, int64_t nrec, int64_t stride, int K, int64_t first, int64_t rows,
                            int32_t* out, hipStream_t st);
+
+// ---- launch shape of a dense reduce ----
+// Vector geometry of a value type: elements per 16-B vector, bytes per element.
+struct VecGeom {
+    int vec, elem;
+    constexpr int chunk() const { return 64 * vec; }  // elements of one wave-wide 1-KiB chunk
+    // the flat kernels' rows: whole vectors, under 4 KiB
+    constexpr bool flat_row(int32_t cols) const { return cols % vec == 0 && (int64_t)cols * elem < 4096; }
+};
+constexpr VecGeom vec_geom(int vtype) { return vtype == kF64 ? VecGeom{2, 8} : VecGeom{4, 4}; }
+// Rows a wave of the flat kernels owns: J 16-B vectors per lane over rows of nv vectors.
+constexpr int rows_per_wave(int J, int nv) {
+    const int r = J * 64 / (nv > 0 ? nv : 1);
+    return r < 1 ? 1 : r > 16 ? 16 : r;
+}
+enum ReduceFamily : int { kFamReduce = 0, kFamRows = 1 };             // k_reduce, k_reduce_rows
+enum StorePolicy : int { kStCached = 0, kStNt = 1, kStThrough = 2 };  // shard stores (k_reduce_rows' SNT)
+// Everything launch_reduce decides from (value type, mode, width) for the kernels it
+// picks by shape: one row of kReduceShapes (dml_kernels.hip) plus the facts derived from
+// the width. The flat family is chosen per chunk (use_flat) and is not described here.
+struct ReduceShape {
+    ReduceFamily family;
+    int group;      // k_reduce: pushes in flight per wave (G)
+    int depth;      // k_reduce_rows: 1 = one push at a time, 3 = pair-packed load groups
+    int cpw;        // consecutive 1-KiB chunks of a row per wave
+    int rpw;        // neighbouring rows per wave
+    int wpb;        // waves per block
+    bool nt_loads;  // non-temporal record loads
+    StorePolicy store;
+    bool full;      // every chunk whole: no column masks
+    int bpc;        // blocks-per-CU cap (unused dynamic LDS), 0 = none
+    // derived by reduce_shape()
+    int row;        // index in kReduceShapes
+    int vec;        // elements per 16-B vector
+    int32_t nchunks;  // 1-KiB chunks per row
+    int32_t ngroups;  // waves per row (or per rpw rows)
+    bool one_wave;  // one wave owns all of a row's chunks
+};
+ReduceShape reduce_shape(int vtype, int mode, int32_t cols);
+
+// The most maxDelta candidates one AdaGrad apply writes (the candidate buffer's size).
 int64_t reduce_blocks(int vtype, int64_t rows, int32_t cols);
 // True when launch_reduce(vtype, mode, cols) runs k_reduce_rows in a plain-sum mode,
 // which rewrites every slot it reads to -1 (the next batch's index then needs no memset).
@@ -425,7 +466,7 @@ uint64_t splitmix64(uint64_t x);
 
 // Name of the dominant kernel (reduce / flat / AdaGrad / sparse leaf) the calling
 // thread launched last, in rocprof's form, e.g.
-// "dml::k_reduce_rows<float, 0, 4, 4, true, true, 1, 4, 0>": bench.py ties a profile's
+// "dml::k_reduce_rows<float, 0, 4, 4, true, true, 1, 4, 2>": bench.py ties a profile's
 // counted HBM bytes to the instantiation that ran (dml_store_kernel_name).
 extern thread_local const char* g_kernel_name;
 inline std::string kname_arg(bool v) { return v ? "true" : "false"; }

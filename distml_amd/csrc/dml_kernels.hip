@@ -9,7 +9,21 @@
 //   k_reduce<T,M>   ordered multi-push reduce: every element of a shard row
 //                   summed over the batch's pushes in push order, one RMW of
 //                   the row (FloatMatrixStore.java:210-222, IntMatrixStore.java:164-178,
-//                   DoubleMatrixStore.java:163-175, FloatMatrixStoreAdaGrad.java:249-284)
+//                   DoubleMatrixStore.java:163-175, FloatMatrixStoreAdaGrad.java:249-284).
+//                   One row and chunk per wave: AdaGrad, the int32 rollback, rows
+//                   narrower than one vector
+//   k_reduce_rows   the same sums of the plain modes with several neighbouring rows
+//                   and chunks per wave (FULL / DEPTH 3 shapes): every other width
+//   k_reduce_flat, k_flat_ident  rows under 4 KiB of whole vectors whose pushes are
+//                   dense: several whole rows per wave; k_flat_ident where the host
+//                   has seen every push to be the identity (record r = row r)
+//   k_ada_flat, k_ada_ident  the AdaGrad counterparts, chunks of at most 4 pushes
+//                   (launch_reduce picks among all of these: reduce_shape() and the
+//                   kReduceShapes table for k_reduce / k_reduce_rows, use_flat() per
+//                   chunk for the flat family)
+//   k_ident_check, k_ident_full, k_assign_cols  the index-chain kernels of identity
+//                   speculation and slot reuse (which pushes need no key index)
+//   k_moments_flat, k_ada_moments  the sharded two-moment AdaGrad pieces and apply
 //   k_array_rollback int32 array stores: undo every add after the first negative
 //                   counter (IntArrayStore.java:97-113); the arrays' ordered
 //                   scatter-add itself is the partition + leaf path of dml_sparse.hip
@@ -31,6 +45,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
+#include <utility>
 
 namespace dml {
 
@@ -1610,159 +1625,217 @@ inline unsigned lds_for_blocks_per_cu(int bpc) { return bpc > 0 ? kLdsPerCU / (u
 // Grid of the int32 rollback: 256 CUs x 8 four-wave blocks; its waves stride over the tasks.
 constexpr int64_t kRollbackBlocks = 2048;
 
-template <typename T, int MODE, int G = 8, bool NT = false, int WPB = 4, int SNT = 0, int CPW = 1, int RPW = 1,
-          bool FULL = false>
-static hipError_t launch_reduce_t(void* shard, int64_t rows, int32_t cols, const Batch& bt, int nb,
-                                  int64_t stride, int K, const int32_t* slot, const uint32_t* rowflag, Ctrl* ctrl,
-                                  uint64_t tail_cut,
-                                  const AdaArgs& ada, hipStream_t st, int64_t* nblocks_out, LaunchEv ev = {},
-                                  RowMap rm = {}, int bpc = 0) {
-    constexpr int VEC = Elem<T>::VEC;
-    const int32_t nchunks = (cols + 64 * VEC - 1) / (64 * VEC);
-    const int32_t ngroups = (nchunks + CPW - 1) / CPW;
-    const int64_t ntask = (rows + RPW - 1) / RPW * ngroups;
-    int64_t nblocks = (ntask + WPB - 1) / WPB;
-    if constexpr (MODE == kRollbackI32) nblocks = std::min<int64_t>(nblocks, kRollbackBlocks);  // its waves stride
-    if (nblocks_out) *nblocks_out = nblocks;
-    if (nblocks <= 0) return hipSuccess;
-    // blocks per CU: the shape's cap (unused dynamic LDS), 0 = none
-    const unsigned occ_lds = lds_for_blocks_per_cu(bpc);
-    if constexpr (RPW > 1) {
-        static_assert(MODE != kAdaGrad && MODE != kRollbackI32, "k_reduce_rows shapes");
-        static const std::string kn =
-            kname("k_reduce_rows", type_name<T>(), MODE, CPW, RPW, NT, FULL, G == 3 ? 3 : 1, WPB, SNT);
-        g_kernel_name = kn.c_str();
-        if (ev.start || ev.stop)
-            hipExtLaunchKernelGGL((k_reduce_rows<T, MODE, CPW, RPW, NT, FULL, G == 3 ? 3 : 1, WPB, SNT>), dim3((unsigned)nblocks),
-                                  dim3(64 * WPB), occ_lds, st, ev.start, ev.stop, 0, (T*)shard, rows, cols, ngroups, bt, nb, stride,
-                                  K, const_cast<int32_t*>(slot), rowflag, ctrl, tail_cut, rm);
-        else
-            hipLaunchKernelGGL((k_reduce_rows<T, MODE, CPW, RPW, NT, FULL, G == 3 ? 3 : 1, WPB, SNT>), dim3((unsigned)nblocks),
-                               dim3(64 * WPB), occ_lds, st, (T*)shard, rows, cols, ngroups, bt, nb, stride, K, const_cast<int32_t*>(slot), rowflag,
-                               ctrl, tail_cut, rm);
-    } else {
-        static const std::string kn = kname("k_reduce", type_name<T>(), MODE, G, NT, WPB, SNT != 0, CPW);
-        g_kernel_name = kn.c_str();
-        if (ev.start || ev.stop)
-            hipExtLaunchKernelGGL((k_reduce<T, MODE, G, NT, WPB, SNT, CPW>), dim3((unsigned)nblocks), dim3(64 * WPB),
-                                  occ_lds, st, ev.start, ev.stop, 0, (T*)shard, rows, cols, ngroups, bt, nb, stride,
-                                  K, slot, rowflag, ctrl, tail_cut, ada, rm);
-        else
-            hipLaunchKernelGGL((k_reduce<T, MODE, G, NT, WPB, SNT, CPW>), dim3((unsigned)nblocks), dim3(64 * WPB),
-                               occ_lds, st, (T*)shard, rows, cols, ngroups, bt, nb, stride, K, slot, rowflag, ctrl,
-                               tail_cut, ada, rm);
-    }
+// One launch of `kernel`: its start / stop events ride in the dispatch packet when the
+// caller carries any (hipExtLaunchKernel); a plain launch otherwise.
+template <typename... KA, typename... A>
+static inline hipError_t launch_k(void (*kernel)(KA...), dim3 grid, dim3 block, unsigned lds, hipStream_t st,
+                                  LaunchEv ev, const A&... a) {
+    if (ev.start || ev.stop)
+        hipExtLaunchKernelGGL(kernel, grid, block, lds, st, ev.start, ev.stop, 0, static_cast<KA>(a)...);
+    else
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<KA>(a)...);
     return hipGetLastError();
 }
 
-// Shape rule (measured, scripts/ubench_reduce.hip, scripts/exp_variants.py): a
-// wave owns RPW neighbouring rows and walks up to CPW = 4 neighbouring 1-KiB
-// chunks of each, RPW x CPW 16-B nt loads of one push in flight. Whole 4-KiB
-// rows: RPW = 2 with the CU capped at 2 blocks (8 waves, 64 KiB of loads in
-// flight); other widths RPW = 4 at their register-limited occupancy. AdaGrad and
-// the int32 rollback keep one row and one chunk per wave (k_reduce: their
-// per-element state triples the registers).
-template <typename T, int MODE>
-static hipError_t launch_auto(void* shard, int64_t rows, int32_t cols, const Batch& bt, int nb, int64_t stride, int K,
-                              const int32_t* slot, const uint32_t* rowflag, Ctrl* ctrl, uint64_t tail_cut,
-                              const AdaArgs& ada, hipStream_t st, int64_t* nblocks_out, LaunchEv ev, RowMap rm) {
-    constexpr int VEC = Elem<T>::VEC;
-    const int32_t nchunks = (cols + 64 * VEC - 1) / (64 * VEC);
-#define DML_L(G, CPW, RPW) launch_reduce_t<T, MODE, G, true, 4, false, CPW, RPW>(shard, rows, cols, bt, nb, stride, K, \
-                                                     slot, rowflag, ctrl, tail_cut, ada, st, nblocks_out, ev, rm)
-// whole-chunk rows store write-through (SNT 2, stg16_wt): no dirty L2 lines for the
-// kernel-end writeback, so the next reduce on the stream starts sooner (config 2:
-// 0.3455 -> 0.3365 ms/step with sampled timing, same box)
-#define DML_LF(G, CPW, RPW, BPC) launch_reduce_t<T, MODE, G, true, 4, 2, CPW, RPW, true>(shard, rows, cols, bt, nb, \
-                                                     stride, K, slot, rowflag, ctrl, tail_cut, ada, st, nblocks_out, ev, rm, BPC)
-    if constexpr (MODE == kAdaGrad) {
-        // G8 with nt shard / delta / alpha traffic (measured best: G4 +10 %, G16 +35 %,
-        // 8-wave blocks +15 %, cached stores slower). The candidate buffer
-        // holds one entry per 4-wave block.
-        return launch_reduce_t<T, MODE, 8, true, 4, true, 1, 1>(shard, rows, cols, bt, nb, stride, K, slot, rowflag,
-                                                                ctrl, tail_cut, ada, st, nblocks_out, ev, rm);
-    } else if constexpr (MODE == kRollbackI32) {
-        return DML_L(8, 1, 1);
-    } else {
-        if (cols < VEC) return DML_L(16, 1, 1);  // narrower than one vector: k_reduce's generic path
-        // whole 4-KiB rows: four rows per wave and at most 8 waves per CU (128 KiB of
-        // loads in flight per CU): config 2 355.7-358.3 us against 362.6-367.7 us for
-        // two rows at 8 waves, 381 us for four rows uncapped or at 12 waves, 367 us at
-        // 6 waves; 1-wave blocks at 8 per CU equal
-        if (cols % (64 * VEC * 4) == 0) return DML_LF(1, 4, 4, 2);
-        // Other widths: pair-packed load groups (DEPTH 3) over 4 rows per wave.
-        // Non-temporal shard stores (the rows are written once per batch): config 5
-        // 460 -> 433 us; config 2's FULL shape measured no gain from them (it stores
-        // write-through, DML_LF above).
-#define DML_LN(G, CPW, RPW) launch_reduce_t<T, MODE, G, true, 4, 1, CPW, RPW>(shard, rows, cols, bt, nb, stride, K, \
-                                                     slot, rowflag, ctrl, tail_cut, ada, st, nblocks_out, ev, rm)
-#define DML_LFN(G, CPW, RPW) launch_reduce_t<T, MODE, G, true, 4, 1, CPW, RPW, true>(shard, rows, cols, bt, nb, \
-                                                     stride, K, slot, rowflag, ctrl, tail_cut, ada, st, nblocks_out, ev, rm, 0)
-        // (kChain and kChainCheckI32 keep the pre-reduce instantiation's loads and stores of
-        // each shape below)
-        if (MODE != kPreReduce && MODE != kChain && MODE != kChainCheckI32) {
-            // Rows of >= 4 chunks that do not fill them (config 5's 4000-B int32 rows in
-            // 4004-B records): cached record loads (the line two neighbouring records
-            // share is fetched once) and 2-wave blocks (a finished block frees its slot
-            // sooner): config 5 428 -> 400 us, 0.565 -> 0.604 of peak, measured against
-            // nt loads, 1/4/8-wave blocks, CPW 1/2, RPW 2, cached stores.
-            if (nchunks >= 4)
-                return launch_reduce_t<T, MODE, 3, false, kC5Wpb, 1, 4, kC5Rpw>(shard, rows, cols, bt, nb, stride, K,
-                                                                               slot, rowflag, ctrl, tail_cut, ada, st,
-                                                                               nblocks_out, ev, rm);
-            if (cols % (64 * VEC * 2) == 0) return DML_LFN(1, 2, 4);
-            if (nchunks >= 2) return DML_LN(3, 2, 4);
-            if (cols % (64 * VEC) == 0) return DML_LFN(1, 1, 4);
-            return DML_LN(3, 1, 4);
-        }
-#undef DML_LN
-#undef DML_LFN
-        if (nchunks >= 4) return DML_L(3, 4, 4);
-        if (cols % (64 * VEC * 2) == 0) return DML_LF(1, 2, 4, 0);
-        if (nchunks >= 2) return DML_L(3, 2, 4);
-        if (cols % (64 * VEC) == 0) return DML_LF(1, 1, 4, 0);
-        return DML_L(3, 1, 4);
-    }
-#undef DML_L
-#undef DML_LF
+// The arguments of a dense reduce launch, as launch_reduce receives them.
+struct ReduceArgs {
+    void* shard;
+    int64_t rows;
+    int32_t cols;
+    const Batch& bt;
+    int nb;
+    int64_t stride;
+    int K;
+    const int32_t* slot;
+    const uint32_t* rowflag;
+    Ctrl* ctrl;
+    uint64_t tail_cut;
+    const AdaArgs& ada;
+    hipStream_t st;
+    int64_t* nblocks_out;
+    LaunchEv ev;
+    RowMap rm;
+};
+
+// The launch shapes of k_reduce and k_reduce_rows, one row each; reduce_shape() below
+// picks the row of a (mode, width). Shape rule (measured, scripts/ubench_reduce.hip,
+// scripts/exp_variants.py): a wave owns RPW neighbouring rows and walks up to CPW = 4
+// neighbouring 1-KiB chunks of each, RPW x CPW 16-B nt loads of one push in flight.
+// AdaGrad and the int32 rollback keep one row and one chunk per wave (k_reduce: their
+// per-element state triples the registers). Rows that are whole chunks run FULL at
+// DEPTH 1, the others pair-packed load groups (DEPTH 3), both over 4 rows per wave.
+// The rows a store applies (kAdd, kAddCheckI32) are written once per batch, so their
+// shapes store non-temporally; the pieces of a pre-reduce or a chained step (kPreReduce,
+// kChain, kChainCheckI32) share the pre-reduce instantiation's loads and stores.
+enum ShapeRow : int {
+    kShNarrow, kShWhole4,
+    kShRag4Nt, kShWhole2Nt, kShRag2Nt, kShWhole1Nt, kShRag1Nt,  // a store's rows
+    kShRag4, kShWhole2, kShRag2, kShWhole1, kShRag1,            // a piece's rows
+    kShAda, kShRollback, kShapeRows
+};
+constexpr ReduceShape kReduceShapes[kShapeRows] = {
+    // family, group, depth, cpw, rpw, wpb, nt loads, store, full, blocks per CU
+    // narrower than one vector: k_reduce's generic path
+    {kFamReduce, 16, 0, 1, 1, 4, true, kStCached, false, 0},  // kShNarrow
+    // whole 4-KiB rows: four rows per wave and at most 8 waves per CU (128 KiB of
+    // loads in flight per CU): config 2 355.7-358.3 us against 362.6-367.7 us for
+    // two rows at 8 waves, 381 us for four rows uncapped or at 12 waves, 367 us at
+    // 6 waves; 1-wave blocks at 8 per CU equal. Whole-chunk rows store
+    // write-through (stg16_wt): no dirty L2 lines for the kernel-end writeback, so
+    // the next reduce on the stream starts sooner (config 2: 0.3455 -> 0.3365 ms/step
+    // with sampled timing, same box)
+    {kFamRows, 0, 1, 4, 4, 4, true, kStThrough, true, 2},  // kShWhole4
+    // A store's other widths. Non-temporal shard stores: config 5 460 -> 433 us;
+    // config 2's FULL shape measured no gain from them (it stores write-through).
+    // Rows of >= 4 chunks that do not fill them (config 5's 4000-B int32 rows in
+    // 4004-B records): cached record loads (the line two neighbouring records
+    // share is fetched once) and 2-wave blocks (a finished block frees its slot
+    // sooner): config 5 428 -> 400 us, 0.565 -> 0.604 of peak, measured against
+    // nt loads, 1/4/8-wave blocks, CPW 1/2, RPW 2, cached stores.
+    {kFamRows, 0, 3, 4, kC5Rpw, kC5Wpb, false, kStNt, false, 0},  // kShRag4Nt
+    {kFamRows, 0, 1, 2, 4, 4, true, kStNt, true, 0},  // kShWhole2Nt
+    {kFamRows, 0, 3, 2, 4, 4, true, kStNt, false, 0},  // kShRag2Nt
+    {kFamRows, 0, 1, 1, 4, 4, true, kStNt, true, 0},  // kShWhole1Nt
+    {kFamRows, 0, 3, 1, 4, 4, true, kStNt, false, 0},  // kShRag1Nt
+    // A piece's other widths: cached stores, write-through where the chunks are whole.
+    {kFamRows, 0, 3, 4, 4, 4, true, kStCached, false, 0},  // kShRag4
+    {kFamRows, 0, 1, 2, 4, 4, true, kStThrough, true, 0},  // kShWhole2
+    {kFamRows, 0, 3, 2, 4, 4, true, kStCached, false, 0},  // kShRag2
+    {kFamRows, 0, 1, 1, 4, 4, true, kStThrough, true, 0},  // kShWhole1
+    {kFamRows, 0, 3, 1, 4, 4, true, kStCached, false, 0},  // kShRag1
+    // AdaGrad: G8 with nt shard / delta / alpha traffic (measured best: G4 +10 %, G16
+    // +35 %, 8-wave blocks +15 %, cached stores slower). The candidate
+    // buffer holds one entry per 4-wave block.
+    {kFamReduce, 8, 0, 1, 1, 4, true, kStNt, false, 0},  // kShAda
+    // the int32 rollback: a capped grid (kRollbackBlocks) whose waves stride over the tasks
+    {kFamReduce, 8, 0, 1, 1, 4, false, kStCached, false, 0},  // kShRollback
+};
+// The modes a row's kernel is instantiated for.
+constexpr bool shape_row_runs(int row, int mode) {
+    return row == kShAda ? mode == kAdaGrad
+           : row == kShRollback ? mode == kRollbackI32
+                                : mode != kAdaGrad && mode != kRollbackI32;
 }
+
+ReduceShape reduce_shape(int vtype, int mode, int32_t cols) {
+    const VecGeom g = vec_geom(vtype);
+    const int32_t nchunks = (cols + g.chunk() - 1) / g.chunk();
+    const bool piece = mode == kPreReduce || mode == kChain || mode == kChainCheckI32;
+    int row;
+    if (mode == kAdaGrad) row = kShAda;
+    else if (mode == kRollbackI32) row = kShRollback;
+    else if (cols < g.vec) row = kShNarrow;
+    else if (cols % (4 * g.chunk()) == 0) row = kShWhole4;
+    else if (nchunks >= 4) row = piece ? kShRag4 : kShRag4Nt;
+    else if (cols % (2 * g.chunk()) == 0) row = piece ? kShWhole2 : kShWhole2Nt;
+    else if (nchunks >= 2) row = piece ? kShRag2 : kShRag2Nt;
+    else if (cols % g.chunk() == 0) row = piece ? kShWhole1 : kShWhole1Nt;
+    else row = piece ? kShRag1 : kShRag1Nt;
+    ReduceShape s = kReduceShapes[row];
+    s.row = row;
+    s.vec = g.vec;
+    s.nchunks = nchunks;
+    s.ngroups = (nchunks + s.cpw - 1) / s.cpw;
+    s.one_wave = s.ngroups <= 1;
+    return s;
+}
+
+// Blocks of a shape's launch over `rows` rows: one wave per (rpw rows, cpw chunks).
+static int64_t shape_blocks(const ReduceShape& s, int64_t rows) {
+    const int64_t ntask = (rows + s.rpw - 1) / s.rpw * s.ngroups;
+    return (ntask + s.wpb - 1) / s.wpb;
+}
+
+// Launches row ROW of the table: the row's fields are the kernel's template arguments
+// and the fields of its name.
+template <typename T, int MODE, int ROW>
+static hipError_t launch_reduce_t(const ReduceShape& s, const ReduceArgs& a) {
+    if constexpr (!shape_row_runs(ROW, MODE)) {
+        return hipErrorInvalidValue;
+    } else {
+        constexpr ReduceShape S = kReduceShapes[ROW];
+        int64_t nblocks = shape_blocks(s, a.rows);
+        if constexpr (MODE == kRollbackI32) nblocks = std::min<int64_t>(nblocks, kRollbackBlocks);  // its waves stride
+        if (a.nblocks_out) *a.nblocks_out = nblocks;
+        if (nblocks <= 0) return hipSuccess;
+        const dim3 grid((unsigned)nblocks), block(64 * S.wpb);
+        const unsigned occ_lds = lds_for_blocks_per_cu(S.bpc);
+        if constexpr (S.family == kFamRows) {
+            static const std::string kn = kname("k_reduce_rows", type_name<T>(), MODE, S.cpw, S.rpw, S.nt_loads, S.full,
+                                                S.depth, S.wpb, (int)S.store);
+            g_kernel_name = kn.c_str();
+            return launch_k(k_reduce_rows<T, MODE, S.cpw, S.rpw, S.nt_loads, S.full, S.depth, S.wpb, S.store>, grid,
+                            block, occ_lds, a.st, a.ev, (T*)a.shard, a.rows, a.cols, s.ngroups, a.bt, a.nb, a.stride,
+                            a.K, const_cast<int32_t*>(a.slot), a.rowflag, a.ctrl, a.tail_cut, a.rm);
+        } else {
+            constexpr bool SNT = S.store != kStCached;
+            static const std::string kn = kname("k_reduce", type_name<T>(), MODE, S.group, S.nt_loads, S.wpb, SNT, S.cpw);
+            g_kernel_name = kn.c_str();
+            return launch_k(k_reduce<T, MODE, S.group, S.nt_loads, S.wpb, SNT, S.cpw>, grid, block, occ_lds, a.st,
+                            a.ev, (T*)a.shard, a.rows, a.cols, s.ngroups, a.bt, a.nb, a.stride, a.K, a.slot,
+                            a.rowflag, a.ctrl, a.tail_cut, a.ada, a.rm);
+        }
+    }
+}
+template <typename T, int MODE, int... ROW>
+static hipError_t launch_auto(const ReduceShape& s, const ReduceArgs& a, std::integer_sequence<int, ROW...>) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((s.row == ROW && ((e = launch_reduce_t<T, MODE, ROW>(s, a)), true)) || ...);
+    return e;
+}
+
+// Calls f(type tag, mode constant) for the (value type, mode) pairs a kernel family is
+// instantiated for; any other pair is hipErrorInvalidValue. FLAT: k_reduce_flat and
+// k_flat_ident, which sum plainly (k_ada_flat has its own launcher).
+constexpr bool pair_legal(bool flat, int vtype, int mode) {
+    const bool fp = vtype == kF32 || vtype == kF64;
+    if (mode == kAdd || mode == kPreReduce) return fp || vtype == kI32;
+    if (mode == kChain) return fp;
+    if (flat) return false;
+    return mode == kAdaGrad ? vtype == kF32 : (mode == kAddCheckI32 || mode == kChainCheckI32) && vtype == kI32;
+}
+template <typename T> struct TypeTag { using type = T; };
+template <bool FLAT, typename T, int VT, typename F, int... M>
+static hipError_t with_mode(int mode, F& f, std::integer_sequence<int, M...>) {
+    hipError_t e = hipErrorInvalidValue;
+    auto call = [&](auto m) {
+        if constexpr (pair_legal(FLAT, VT, decltype(m)::value)) e = f(TypeTag<T>{}, m);
+    };
+    (void)((mode == M && (call(std::integral_constant<int, M>{}), true)) || ...);
+    return e;
+}
+template <bool FLAT, typename F>
+static hipError_t with_type_mode(int vtype, int mode, F f) {
+    using Modes = std::make_integer_sequence<int, kChainCheckI32 + 1>;
+    if (vtype == kF32) return with_mode<FLAT, float, kF32>(mode, f, Modes{});
+    if (vtype == kI32) return with_mode<FLAT, int32_t, kI32>(mode, f, Modes{});
+    if (vtype == kF64) return with_mode<FLAT, double, kF64>(mode, f, Modes{});
+    return hipErrorInvalidValue;
+}
+
+// Blocks of a flat launch: R rows per wave, nw waves per block.
+static int64_t flat_blocks(int64_t rows, int R, int nw) { return ((rows + R - 1) / R + nw - 1) / nw; }
 
 // k_reduce_flat launch (narrow dense rows, see the kernel): R rows per wave.
-template <typename T, int MODE, int JMAX, int PB>
-static hipError_t launch_flat_t(void* shard, int64_t rows, int32_t cols, const Batch& bt, int nb, int64_t stride,
-                                int K, const int32_t* slot, const uint32_t* rowflag, Ctrl* ctrl, uint64_t tail_cut,
-                                hipStream_t st, int64_t* nblocks_out, LaunchEv ev, RowMap rm) {
-    constexpr int VEC = Elem<T>::VEC;
-    const int NV = cols / VEC;
-    const int R = std::max(1, std::min(16, JMAX * 64 / NV));
-    const int64_t nblocks = ((rows + R - 1) / R + 3) / 4;
-    if (nblocks_out) *nblocks_out = nblocks;
-    if (nblocks <= 0) return hipSuccess;
-    static const std::string kn = kname("k_reduce_flat", type_name<T>(), MODE, JMAX, PB);
-    g_kernel_name = kn.c_str();
-    if (ev.start || ev.stop)
-        hipExtLaunchKernelGGL((k_reduce_flat<T, MODE, JMAX, PB>), dim3((unsigned)nblocks), dim3(256), 0, st, ev.start,
-                              ev.stop, 0, (T*)shard, rows, cols, R, bt, nb, stride, K, const_cast<int32_t*>(slot),
-                              rowflag, ctrl, tail_cut, rm);
-    else
-        hipLaunchKernelGGL((k_reduce_flat<T, MODE, JMAX, PB>), dim3((unsigned)nblocks), dim3(256), 0, st, (T*)shard,
-                           rows, cols, R, bt, nb, stride, K, const_cast<int32_t*>(slot), rowflag, ctrl, tail_cut, rm);
-    return hipGetLastError();
-}
-
 // One push per round: JMAX 8 (R = 10 rows at 200 columns) measured within 2 % of
 // 4 x 1, 4 x 2, 8 x 2 and 4 x 4 (config 4, ascending and permuted), and of
 // occupancy caps at 1-3 blocks per CU (all slower); nt record loads 2-3 % faster
-// than cached ones; JMAX 12 (below) beat 8 on permuted pushes.
+// than cached ones; JMAX 12 beat 8 on permuted pushes.
+// JMAX 12: config 4's 800-B rows as 15 rows per wave (750 of 768 vector slots);
+// permuted pushes 4 775-4 801 -> 4 905-4 925 GiB/s against JMAX 8 (10 rows),
+// ascending equal, JMAX 16 in between (same box, 2 rounds)
 template <typename T, int MODE>
-static hipError_t launch_flat(void* shard, int64_t rows, int32_t cols, const Batch& bt, int nb, int64_t stride, int K,
-                              const int32_t* slot, const uint32_t* rowflag, Ctrl* ctrl, uint64_t tail_cut,
-                              hipStream_t st, int64_t* nblocks_out, LaunchEv ev, RowMap rm) {
-    // JMAX 12: config 4's 800-B rows as 15 rows per wave (750 of 768 vector slots);
-    // permuted pushes 4 775-4 801 -> 4 905-4 925 GiB/s against JMAX 8 (10 rows),
-    // ascending equal, JMAX 16 in between (same box, 2 rounds)
-    return launch_flat_t<T, MODE, 12, 1>(shard, rows, cols, bt, nb, stride, K, slot, rowflag, ctrl, tail_cut, st,
-                                         nblocks_out, ev, rm);
+static hipError_t launch_flat(const ReduceArgs& a) {
+    constexpr int JMAX = 12, PB = 1;
+    const int R = rows_per_wave(JMAX, a.cols / Elem<T>::VEC);
+    const int64_t nblocks = flat_blocks(a.rows, R, 4);
+    if (a.nblocks_out) *a.nblocks_out = nblocks;
+    if (nblocks <= 0) return hipSuccess;
+    static const std::string kn = kname("k_reduce_flat", type_name<T>(), MODE, JMAX, PB);
+    g_kernel_name = kn.c_str();
+    return launch_k(k_reduce_flat<T, MODE, JMAX, PB>, dim3((unsigned)nblocks), dim3(256), 0, a.st, a.ev, (T*)a.shard,
+                    a.rows, a.cols, R, a.bt, a.nb, a.stride, a.K, const_cast<int32_t*>(a.slot), a.rowflag, a.ctrl,
+                    a.tail_cut, a.rm);
 }
 
 // k_flat_ident launch: the all-identity chunks of the flat shape (the host checked
@@ -1773,45 +1846,24 @@ static hipError_t launch_flat(void* shard, int64_t rows, int32_t cols, const Bat
 constexpr int kFlatIdentJ = 8;  // 16-B vectors per lane
 
 int flat_ident_rows_per_wave(int vtype, int32_t cols) {
-    const int NV = cols / (vtype == kF64 ? 2 : 4);
-    return std::max(1, std::min(16, kFlatIdentJ * 64 / std::max(NV, 1)));
-}
-
-template <typename T, int MODE>
-static hipError_t launch_flat_ident_t(void* shard, int64_t rows, int32_t cols, const Batch& bt, int nb,
-                                      int64_t stride, int K, Ctrl* ctrl, hipStream_t st, int64_t* nblocks_out,
-                                      LaunchEv ev, RowMap rm) {
-    constexpr int VEC = Elem<T>::VEC, J = kFlatIdentJ, D = 3, NW = kFlatIdentWaves;  // D: pushes in flight
-    const int NV = cols / VEC;
-    const int R = std::max(1, std::min(16, J * 64 / NV));
-    const int64_t nblocks = ((rows + R - 1) / R + NW - 1) / NW;
-    if (nblocks_out) *nblocks_out = nblocks;
-    if (nblocks <= 0) return hipSuccess;
-    static const std::string kn = kname("k_flat_ident", type_name<T>(), MODE, J, D, NW);
-    g_kernel_name = kn.c_str();
-    if (ev.start || ev.stop)
-        hipExtLaunchKernelGGL((k_flat_ident<T, MODE, J, D, NW>), dim3((unsigned)nblocks), dim3(NW * 64), 0, st,
-                              ev.start, ev.stop, 0, (T*)shard, rows, cols, R, bt, nb, stride, K, ctrl, rm);
-    else
-        hipLaunchKernelGGL((k_flat_ident<T, MODE, J, D, NW>), dim3((unsigned)nblocks), dim3(NW * 64), 0, st,
-                           (T*)shard, rows, cols, R, bt, nb, stride, K, ctrl, rm);
-    return hipGetLastError();
+    return rows_per_wave(kFlatIdentJ, cols / vec_geom(vtype).vec);
 }
 
 hipError_t launch_flat_ident(int vtype, int mode, void* shard, int64_t rows, int32_t cols, const Batch& bt, int nb,
                              int64_t stride, int K, Ctrl* ctrl, hipStream_t st, int64_t* nblocks_out, LaunchEv ev,
                              RowMap rm) {
-#define DML_FI(T, M) launch_flat_ident_t<T, M>(shard, rows, cols, bt, nb, stride, K, ctrl, st, nblocks_out, ev, rm)
-    if (mode == kChain) {
-        if (vtype == kF32) return DML_FI(float, kChain);
-        if (vtype == kF64) return DML_FI(double, kChain);
-        return hipErrorInvalidValue;
-    }
-    if (vtype == kF32) return mode == kAdd ? DML_FI(float, kAdd) : DML_FI(float, kPreReduce);
-    if (vtype == kI32) return mode == kAdd ? DML_FI(int32_t, kAdd) : DML_FI(int32_t, kPreReduce);
-    if (vtype == kF64) return mode == kAdd ? DML_FI(double, kAdd) : DML_FI(double, kPreReduce);
-#undef DML_FI
-    return hipErrorInvalidValue;
+    return with_type_mode<true>(vtype, mode, [&](auto t, auto m) {
+        using T = typename decltype(t)::type;
+        constexpr int MODE = decltype(m)::value, J = kFlatIdentJ, D = 3, NW = kFlatIdentWaves;  // D: pushes in flight
+        const int R = flat_ident_rows_per_wave(vtype, cols);
+        const int64_t nblocks = flat_blocks(rows, R, NW);
+        if (nblocks_out) *nblocks_out = nblocks;
+        if (nblocks <= 0) return hipSuccess;
+        static const std::string kn = kname("k_flat_ident", type_name<T>(), MODE, J, D, NW);
+        g_kernel_name = kn.c_str();
+        return launch_k(k_flat_ident<T, MODE, J, D, NW>, dim3((unsigned)nblocks), dim3(NW * 64), 0, st, ev, (T*)shard,
+                        rows, cols, R, bt, nb, stride, K, ctrl, rm);
+    });
 }
 
 // The flat narrow-row kernels apply to plain sums (and AdaGrad chunks of at most 4
@@ -1821,9 +1873,7 @@ hipError_t launch_flat_ident(int vtype, int mode, void* shard, int64_t rows, int
 bool use_flat(int vtype, int mode, int32_t cols, const Batch& bt, int nb, int64_t rows) {
     if (mode != kAdd && mode != kPreReduce && mode != kChain && !(mode == kAdaGrad && vtype == kF32 && nb <= 4))
         return false;
-    const int VEC = vtype == kF64 ? 2 : 4;
-    const int elem = vtype == kF64 ? 8 : 4;
-    if (cols % VEC || (int64_t)cols * elem >= 4096 || nb <= 0) return false;
+    if (!vec_geom(vtype).flat_row(cols) || nb <= 0) return false;
     for (int b = 0; b < nb; ++b)
         if (2 * bt.nrec[b] < rows) return false;
     return true;
@@ -1844,32 +1894,25 @@ bool flat_ident_ok(const Ctrl& h, const Batch& bt, int nb, int64_t need, uint64_
 // Rows of >= 4 KiB that are not whole 4-KiB multiples run the pair-packed DEPTH-3
 // loop, which checks identity records only: no speculation there.
 bool spec_shape(int vtype, int32_t cols) {
-    const int VEC = vtype == kF64 ? 2 : 4;
-    const int64_t bytes = (int64_t)cols * (vtype == kF64 ? 8 : 4);
-    return bytes % 4096 == 0 || (cols % VEC == 0 && bytes < 4096);
+    return reduce_shape(vtype, kAdd, cols).full || vec_geom(vtype).flat_row(cols);
 }
 
-// k_ada_flat launch: R rows per wave (R = 5 at 200 columns), NW waves per block.
-template <int JMAX, int PB, int NW>
-static hipError_t launch_ada_flat_t(void* shard, int64_t rows, int32_t cols, const Batch& bt, int nb, int64_t stride,
-                                    int K, const int32_t* slot, const uint32_t* rowflag, Ctrl* ctrl,
-                                    uint64_t tail_cut, const AdaArgs& ada, hipStream_t st, int64_t* nblocks_out,
-                                    LaunchEv ev) {
-    const int NV = cols / 4;
-    const int R = std::max(1, std::min(16, JMAX * 64 / NV));
-    const int64_t nblocks = ((rows + R - 1) / R + NW - 1) / NW;
-    if (nblocks_out) *nblocks_out = nblocks;
+// k_ada_flat launch: R rows per wave, NW waves per block.
+// JMAX 4 vectors per lane (R = 5 rows at 200 columns), two pushes per round: for
+// chunks of at most 4 pushes (the exact exchange path's slices at low W) 17.3 ms
+// per 10 M-row config-4 AdaGrad apply of 2 pushes against 19.1 ms for k_reduce;
+// with 8 pushes k_reduce (8 pushes in flight per wave) stays ahead (2.6 vs 2.95 ms).
+static hipError_t launch_ada_flat(const ReduceArgs& a) {
+    constexpr int JMAX = 4, PB = 2, NW = kAdaFlatWaves;
+    const int R = rows_per_wave(JMAX, a.cols / 4);
+    const int64_t nblocks = flat_blocks(a.rows, R, NW);
+    if (a.nblocks_out) *a.nblocks_out = nblocks;
     if (nblocks <= 0) return hipSuccess;
     static const std::string kn = kname("k_ada_flat", JMAX, PB, NW);
     g_kernel_name = kn.c_str();
-    if (ev.start || ev.stop)
-        hipExtLaunchKernelGGL((k_ada_flat<JMAX, PB, NW>), dim3((unsigned)nblocks), dim3(NW * 64), 0, st, ev.start,
-                              ev.stop, 0, (float*)shard, rows, cols, R, bt, nb, stride, K, const_cast<int32_t*>(slot),
-                              rowflag, ctrl, tail_cut, ada);
-    else
-        hipLaunchKernelGGL((k_ada_flat<JMAX, PB, NW>), dim3((unsigned)nblocks), dim3(NW * 64), 0, st, (float*)shard,
-                           rows, cols, R, bt, nb, stride, K, const_cast<int32_t*>(slot), rowflag, ctrl, tail_cut, ada);
-    return hipGetLastError();
+    return launch_k(k_ada_flat<JMAX, PB, NW>, dim3((unsigned)nblocks), dim3(NW * 64), 0, a.st, a.ev, (float*)a.shard,
+                    a.rows, a.cols, R, a.bt, a.nb, a.stride, a.K, const_cast<int32_t*>(a.slot), a.rowflag, a.ctrl,
+                    a.tail_cut, a.ada);
 }
 
 // k_ada_ident: k_ada_flat for the AdaGrad chunks the host has seen to be all identity
@@ -2004,70 +2047,49 @@ __global__ __launch_bounds__(256) void k_ada_ident(float* __restrict__ shard, in
     }
 }
 
-template <int U, int NB>
-static hipError_t launch_ada_ident_t(void* shard, int64_t nvec, int32_t cols, int64_t nblocks, const Batch& bt,
-                                     int64_t stride, int K, const AdaArgs& ada, hipStream_t st, LaunchEv ev) {
-    static const std::string kn = kname("k_ada_ident", U, NB);
-    g_kernel_name = kn.c_str();
-    if (ev.start || ev.stop)
-        hipExtLaunchKernelGGL((k_ada_ident<U, NB>), dim3((unsigned)nblocks), dim3(256), 0, st, ev.start, ev.stop, 0,
-                              (float*)shard, nvec, cols, bt, stride, K, ada);
-    else
-        hipLaunchKernelGGL((k_ada_ident<U, NB>), dim3((unsigned)nblocks), dim3(256), 0, st, (float*)shard, nvec, cols,
-                           bt, stride, K, ada);
-    return hipGetLastError();
+// Blocks of a k_ada_ident launch (one maxDelta candidate each): 256·U vectors per block.
+static int64_t ada_ident_blocks(int64_t rows, int32_t cols) {
+    return (rows * cols / 4 + 256 * kAdaIdentU - 1) / (256 * kAdaIdentU);
 }
 
 // One maxDelta candidate per block: *ncand_out = the blocks launched (<= reduce_blocks(),
 // the candidate buffer's size).
 hipError_t launch_ada_ident(void* shard, int64_t rows, int32_t cols, const Batch& bt, int nb, int64_t stride, int K,
                             const AdaArgs& ada, hipStream_t st, int64_t* ncand_out, LaunchEv ev) {
-    if (nb <= 0 || nb > 4 || cols % 4 || (int64_t)cols * 4 >= 4096) return hipErrorInvalidValue;
+    if (nb <= 0 || nb > 4 || !vec_geom(kF32).flat_row(cols)) return hipErrorInvalidValue;
     constexpr int U = kAdaIdentU;
-    const int64_t nvec = rows * cols / 4, nblocks = (nvec + 256 * U - 1) / (256 * U);
+    const int64_t nvec = rows * cols / 4, nblocks = ada_ident_blocks(rows, cols);
     if (ncand_out) *ncand_out = nblocks;
     if (nblocks <= 0) return hipSuccess;
+    auto launch = [&](auto n) {
+        constexpr int NB = decltype(n)::value;
+        static const std::string kn = kname("k_ada_ident", U, NB);
+        g_kernel_name = kn.c_str();
+        return launch_k(k_ada_ident<U, NB>, dim3((unsigned)nblocks), dim3(256), 0, st, ev, (float*)shard, nvec, cols,
+                        bt, stride, K, ada);
+    };
     switch (nb) {
-        case 1: return launch_ada_ident_t<U, 1>(shard, nvec, cols, nblocks, bt, stride, K, ada, st, ev);
-        case 2: return launch_ada_ident_t<U, 2>(shard, nvec, cols, nblocks, bt, stride, K, ada, st, ev);
-        case 3: return launch_ada_ident_t<U, 3>(shard, nvec, cols, nblocks, bt, stride, K, ada, st, ev);
-        default: return launch_ada_ident_t<U, 4>(shard, nvec, cols, nblocks, bt, stride, K, ada, st, ev);
+        case 1: return launch(std::integral_constant<int, 1>{});
+        case 2: return launch(std::integral_constant<int, 2>{});
+        case 3: return launch(std::integral_constant<int, 3>{});
+        default: return launch(std::integral_constant<int, 4>{});
     }
 }
 
-// JMAX 4 vectors per lane (R = 5 rows at 200 columns), two pushes per round: for
-// chunks of at most 4 pushes (the exact exchange path's slices at low W) 17.3 ms
-// per 10 M-row config-4 AdaGrad apply of 2 pushes against 19.1 ms for k_reduce;
-// with 8 pushes k_reduce (8 pushes in flight per wave) stays ahead (2.6 vs 2.95 ms).
-static hipError_t launch_ada_flat(void* shard, int64_t rows, int32_t cols, const Batch& bt, int nb, int64_t stride,
-                                  int K, const int32_t* slot, const uint32_t* rowflag, Ctrl* ctrl, uint64_t tail_cut,
-                                  const AdaArgs& ada, hipStream_t st, int64_t* nblocks_out, LaunchEv ev) {
-    return launch_ada_flat_t<4, 2, kAdaFlatWaves>(shard, rows, cols, bt, nb, stride, K, slot, rowflag, ctrl, tail_cut,
-                                                  ada, st, nblocks_out, ev);
-}
-
 bool reduce_clears_slots(int vtype, int mode, int32_t cols) {
-    if (mode == kAdaGrad) return vtype == kF32 && cols <= 64 * 4;  // k_reduce, one chunk group per row
-    if (mode != kAdd && mode != kPreReduce && mode != kAddCheckI32) return false;
-    const int VEC = vtype == kF64 ? 2 : 4;
-    if (cols < VEC) return false;  // k_reduce's generic path
-    // k_reduce_rows clears only when one wave owns a row's every chunk (launch_auto's
-    // CPW: 4 for whole 4-KiB multiples and for >= 4 chunks, else 2 or 1); the flat
-    // kernel always does, but is chosen per chunk, so it is not counted on here
-    const int64_t nchunks = (cols + 64 * VEC - 1) / (64 * VEC);
-    const int64_t cpw = (nchunks >= 4 || cols % (64 * VEC * 4) == 0) ? 4 : nchunks >= 2 ? 2 : 1;
-    return nchunks <= cpw;
+    const ReduceShape s = reduce_shape(vtype, mode, cols);
+    // k_reduce clears in AdaGrad mode only; k_reduce_rows in the plain-sum modes (the
+    // chained steps keep the table). Both only when one wave owns a row's every chunk.
+    // The flat kernel always does, but is chosen per chunk, so it is not counted on here.
+    if (mode == kAdaGrad) return vtype == kF32 && s.one_wave;
+    return (mode == kAdd || mode == kPreReduce || mode == kAddCheckI32) && s.family == kFamRows && s.one_wave;
 }
 
 int64_t reduce_blocks(int vtype, int64_t rows, int32_t cols) {
-    // The most maxDelta candidates one AdaGrad apply writes (the candidate buffer's size):
-    // k_reduce runs one row and one chunk per wave, 4 waves per block, one candidate per
-    // block; k_ada_flat fewer; k_ada_ident one per block of 256·U vectors.
-    const int VEC = vtype == kF64 ? 2 : 4;
-    const int64_t nchunks = (cols + 64 * VEC - 1) / (64 * VEC);
-    int64_t n = (rows * nchunks + 3) / 4;
-    if (vtype == kF32 && cols >= 4 && cols % 4 == 0 && (int64_t)cols * 4 < 4096)
-        n = std::max(n, (rows * cols / 4 + 256 * kAdaIdentU - 1) / (256 * kAdaIdentU));
+    // k_reduce's AdaGrad shape writes one candidate per block; k_ada_flat fewer;
+    // k_ada_ident, where its width guard lets it run, one per block of 256·U vectors.
+    int64_t n = shape_blocks(reduce_shape(vtype, kAdaGrad, cols), rows);
+    if (vtype == kF32 && cols >= 4 && vec_geom(kF32).flat_row(cols)) n = std::max(n, ada_ident_blocks(rows, cols));
     return n;
 }
 
@@ -2075,48 +2097,27 @@ hipError_t launch_reduce(int vtype, int mode, void* shard, int64_t rows, int32_t
                          int64_t stride, int K, const int32_t* slot, const uint32_t* rowflag, Ctrl* ctrl,
                          uint64_t tail_cut, const AdaArgs& ada, hipStream_t st, int64_t* nblocks_out, LaunchEv ev,
                          RowMap rm) {
-#define DML_A(T, M) launch_auto<T, M>(shard, rows, cols, bt, nb, stride, K, slot, rowflag, ctrl, tail_cut, ada, st, nblocks_out, ev, rm)
-#define DML_F(T, M) launch_flat<T, M>(shard, rows, cols, bt, nb, stride, K, slot, rowflag, ctrl, tail_cut, st, nblocks_out, ev, rm)
+    const ReduceArgs a{shard, rows, cols, bt, nb, stride, K, slot, rowflag, ctrl, tail_cut, ada, st, nblocks_out, ev, rm};
     if (use_flat(vtype, mode, cols, bt, nb, rm.block ? rm.rows_total : rows)) {
         if (mode == kAdaGrad)  // the AdaGrad store runs no row map (exchange path only)
-            return rm.block || rm.out ? hipErrorInvalidValue
-                                      : launch_ada_flat(shard, rows, cols, bt, nb, stride, K, slot, rowflag, ctrl,
-                                                        tail_cut, ada, st, nblocks_out, ev);
-        if (mode == kChain) {
-            if (vtype == kF32) return DML_F(float, kChain);
-            if (vtype == kF64) return DML_F(double, kChain);
-            return hipErrorInvalidValue;
-        }
-        if (vtype == kF32) return mode == kAdd ? DML_F(float, kAdd) : DML_F(float, kPreReduce);
-        if (vtype == kI32) return mode == kAdd ? DML_F(int32_t, kAdd) : DML_F(int32_t, kPreReduce);
-        if (vtype == kF64) return mode == kAdd ? DML_F(double, kAdd) : DML_F(double, kPreReduce);
+            return rm.block || rm.out ? hipErrorInvalidValue : launch_ada_flat(a);
+        return with_type_mode<true>(vtype, mode, [&](auto t, auto m) {
+            return launch_flat<typename decltype(t)::type, decltype(m)::value>(a);
+        });
     }
-#undef DML_F
-    if (vtype == kF32) {
-        if (mode == kAdd) return DML_A(float, kAdd);
-        if (mode == kAdaGrad) return DML_A(float, kAdaGrad);
-        if (mode == kPreReduce) return DML_A(float, kPreReduce);
-        if (mode == kChain) return DML_A(float, kChain);
-    } else if (vtype == kI32) {
-        if (mode == kAdd) return DML_A(int32_t, kAdd);
-        if (mode == kAddCheckI32) return DML_A(int32_t, kAddCheckI32);
-        if (mode == kPreReduce) return DML_A(int32_t, kPreReduce);
-        if (mode == kChainCheckI32) return DML_A(int32_t, kChainCheckI32);
-    } else if (vtype == kF64) {
-        if (mode == kAdd) return DML_A(double, kAdd);
-        if (mode == kPreReduce) return DML_A(double, kPreReduce);
-        if (mode == kChain) return DML_A(double, kChain);
-    }
-#undef DML_A
-    return hipErrorInvalidValue;
+    const ReduceShape s = reduce_shape(vtype, mode, cols);
+    return with_type_mode<false>(vtype, mode, [&](auto t, auto m) {
+        return launch_auto<typename decltype(t)::type, decltype(m)::value>(
+            s, a, std::make_integer_sequence<int, kShapeRows>{});
+    });
 }
 
 hipError_t launch_rollback_i32(int32_t* shard, int64_t rows, int32_t cols, const Batch& bt, int nb,
                                int64_t stride, int K, const int32_t* slot, const uint32_t* rowflag, Ctrl* ctrl,
                                uint64_t tail_cut, hipStream_t st, RowMap rm) {
-    AdaArgs none{};
-    return launch_reduce_t<int32_t, kRollbackI32>(shard, rows, cols, bt, nb, stride, K, slot, rowflag, ctrl,
-                                                  tail_cut, none, st, nullptr, LaunchEv{}, rm);
+    const AdaArgs none{};
+    const ReduceArgs a{shard, rows, cols, bt, nb, stride, K, slot, rowflag, ctrl, tail_cut, none, st, nullptr, LaunchEv{}, rm};
+    return launch_reduce_t<int32_t, kRollbackI32, kShRollback>(reduce_shape(kI32, kRollbackI32, cols), a);
 }
 
 // ---------------------------------------------------------------------------
@@ -2148,12 +2149,7 @@ __global__ __launch_bounds__(64) void k_chain_i32_verdict(const Batch bt, int nb
 
 hipError_t launch_chain_i32_verdict(const Batch& bt, int nb, int64_t stride, int K, Ctrl* ctrl, ChainI32Rec* rec,
                                     int32_t step, hipStream_t st, LaunchEv ev) {
-    if (ev.start || ev.stop)
-        hipExtLaunchKernelGGL(k_chain_i32_verdict, dim3(1), dim3(64), 0, st, ev.start, ev.stop, 0, bt, nb, stride, K,
-                              ctrl, rec, step);
-    else
-        hipLaunchKernelGGL(k_chain_i32_verdict, dim3(1), dim3(64), 0, st, bt, nb, stride, K, ctrl, rec, step);
-    return hipGetLastError();
+    return launch_k(k_chain_i32_verdict, dim3(1), dim3(64), 0, st, ev, bt, nb, stride, K, ctrl, rec, step);
 }
 
 // The owner's commit of a chained int32 slice: a closed home record closes the store's
@@ -2624,8 +2620,7 @@ hipError_t launch_rmw_floor(float* a, const uint32_t* idx, const float* v, int64
     if (n <= 0) return hipSuccess;
     // one update per thread up to 2^28 updates (config 3: 32e6), grid-stride beyond
     const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)1 << 20);
-    hipExtLaunchKernelGGL(k_rmw_floor, dim3(grid), dim3(256), 0, st, ev.start, ev.stop, 0, a, idx, v, n);
-    return hipGetLastError();
+    return launch_k(k_rmw_floor, dim3(grid), dim3(256), 0, st, ev, a, idx, v, n);
 }
 
 // Row-gather floor (diagnostic, config 5): the touched rows of an int32 shard in row
@@ -2676,9 +2671,7 @@ hipError_t launch_gather_floor(int32_t* shard, int32_t cols, const int32_t* trow
                                const uint64_t* addr, int64_t ntouched, hipStream_t st, LaunchEv ev) {
     if (ntouched <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((ntouched + 3) / 4);
-    hipExtLaunchKernelGGL(k_gather_floor, dim3(grid), dim3(256), 0, st, ev.start, ev.stop, 0, shard, cols, trow, tptr,
-                          addr, ntouched);
-    return hipGetLastError();
+    return launch_k(k_gather_floor, dim3(grid), dim3(256), 0, st, ev, shard, cols, trow, tptr, addr, ntouched);
 }
 
 // Dense stream floor (diagnostic, config 4 and its AdaGrad variant): the shard's
@@ -2743,26 +2736,16 @@ hipError_t launch_dense_floor(const float* data, float* out, float* delta, const
     const int64_t nvec = elems / 4;
     if (nvec <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((nvec + 511) / 512);
-    if (delta)
-        hipExtLaunchKernelGGL(k_dense_floor<true>, dim3(grid), dim3(256), 0, st, ev.start, ev.stop, 0, data, out, delta,
-                              bt, nb, stride, K, cols, nvec);
-    else
-        hipExtLaunchKernelGGL(k_dense_floor<false>, dim3(grid), dim3(256), 0, st, ev.start, ev.stop, 0, data, out,
-                              delta, bt, nb, stride, K, cols, nvec);
-    return hipGetLastError();
+    return launch_k(delta ? k_dense_floor<true> : k_dense_floor<false>, dim3(grid), dim3(256), 0, st, ev, data, out,
+                    delta, bt, nb, stride, K, cols, nvec);
 }
 
 hipError_t launch_stream(bool copy, void* dst, const void* src, int64_t n16, hipStream_t st, LaunchEv ev) {
     if (n16 <= 0) return hipSuccess;
     const int64_t want = (n16 + 1023) / 1024;  // one 256-thread block per 4 wave steps
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, 256 * 16));
-    if (copy)
-        hipExtLaunchKernelGGL(k_stream<true>, dim3(grid), dim3(256), 0, st, ev.start, ev.stop, 0, (uint8_t*)dst,
-                              (const uint8_t*)src, n16);
-    else
-        hipExtLaunchKernelGGL(k_stream<false>, dim3(grid), dim3(256), 0, st, ev.start, ev.stop, 0, (uint8_t*)dst,
-                              (const uint8_t*)src, n16);
-    return hipGetLastError();
+    return launch_k(copy ? k_stream<true> : k_stream<false>, dim3(grid), dim3(256), 0, st, ev, (uint8_t*)dst,
+                    (const uint8_t*)src, n16);
 }
 
 // DataStore.rand() distributions (dml_store_rand). f32: (a/100f - 0.5f)/cols,
@@ -2926,19 +2909,13 @@ __global__ __launch_bounds__(256) void k_moments_flat(int64_t ntask, int32_t col
 hipError_t launch_moments(int64_t ntask, int32_t cols, const Batch& bt, int nb, int64_t stride, int K, int32_t* slot,
                           const Ctrl* ctrl, RowMap rm, hipStream_t st, LaunchEv ev) {
     constexpr int JMAX = 8;
-    if (cols % 4 || cols * 4 >= 4096 || !rm.out) return hipErrorInvalidValue;  // the flat shapes
-    const int NV = cols / 4;
-    const int R = std::max(1, std::min(16, JMAX * 64 / NV));
-    const int64_t nblocks = ((ntask + R - 1) / R + 3) / 4;
+    if (!vec_geom(kF32).flat_row(cols) || !rm.out) return hipErrorInvalidValue;  // the flat shapes
+    const int R = rows_per_wave(JMAX, cols / 4);
+    const int64_t nblocks = flat_blocks(ntask, R, 4);
     if (nblocks <= 0) return hipSuccess;
     g_kernel_name = "dml::k_moments_flat<8>";
-    if (ev.start || ev.stop)
-        hipExtLaunchKernelGGL((k_moments_flat<JMAX>), dim3((unsigned)nblocks), dim3(256), 0, st, ev.start, ev.stop, 0,
-                              ntask, cols, R, bt, nb, stride, K, slot, ctrl, rm);
-    else
-        hipLaunchKernelGGL((k_moments_flat<JMAX>), dim3((unsigned)nblocks), dim3(256), 0, st, ntask, cols, R, bt, nb,
-                           stride, K, slot, ctrl, rm);
-    return hipGetLastError();
+    return launch_k(k_moments_flat<JMAX>, dim3((unsigned)nblocks), dim3(256), 0, st, ev, ntask, cols, R, bt, nb,
+                    stride, K, slot, ctrl, rm);
 }
 
 // Owner apply of the reduce-scattered moments ([row][Σu | Σu²], rows x 2 cols):
@@ -3023,11 +3000,8 @@ hipError_t launch_ada_moments(float* shard, const float* src, int64_t rows, int3
                               MaxDelta* md, int64_t first, hipStream_t st, LaunchEv ev) {
     if (cols % 4 || rows <= 0) return hipErrorInvalidValue;
     g_kernel_name = "dml::k_ada_moments";
-    if (ev.start || ev.stop)
-        hipExtLaunchKernelGGL(k_ada_moments, dim3(kMomentBlocks), dim3(256), 0, st, ev.start, ev.stop, 0, shard, src,
-                              rows, cols, ada);
-    else
-        hipLaunchKernelGGL(k_ada_moments, dim3(kMomentBlocks), dim3(256), 0, st, shard, src, rows, cols, ada);
+    const hipError_t e = launch_k(k_ada_moments, dim3(kMomentBlocks), dim3(256), 0, st, ev, shard, src, rows, cols, ada);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_maxdelta_elems, dim3(1), dim3(256), 0, st, ada.cand, (int64_t)kMomentBlocks, md, first, cols);
     return hipGetLastError();
 }
@@ -3250,15 +3224,13 @@ hipError_t launch_chain_ada(bool ident, int64_t ntask, int32_t cols, const Batch
     if (ident) {
         static const std::string kn = kname("k_chain_ada_ident", D);
         g_kernel_name = kn.c_str();
-        hipExtLaunchKernelGGL((k_chain_ada_ident<D>), dim3((unsigned)nblocks), dim3(256), 0, st, ev.start, ev.stop, 0,
-                              ntask * (cols / 4), cols, bt, nb, stride, K, ctrl, rm, ca);
-    } else {
-        static const std::string kn = kname("k_chain_ada_rows", D);
-        g_kernel_name = kn.c_str();
-        hipExtLaunchKernelGGL((k_chain_ada_rows<D>), dim3((unsigned)nblocks), dim3(256), 0, st, ev.start, ev.stop, 0,
-                              ntask, cols, bt, nb, stride, K, slot, ctrl, rm, ca);
+        return launch_k(k_chain_ada_ident<D>, dim3((unsigned)nblocks), dim3(256), 0, st, ev, ntask * (cols / 4), cols,
+                        bt, nb, stride, K, ctrl, rm, ca);
     }
-    return hipGetLastError();
+    static const std::string kn = kname("k_chain_ada_rows", D);
+    g_kernel_name = kn.c_str();
+    return launch_k(k_chain_ada_rows<D>, dim3((unsigned)nblocks), dim3(256), 0, st, ev, ntask, cols, bt, nb, stride, K,
+                    slot, ctrl, rm, ca);
 }
 
 // The owner's commit of its AdaGrad slice when the chain brings it home: shard data
