@@ -9,6 +9,7 @@ from .datadesc import ALL, EMPTY, DataDesc, KeyCollection, KeyList, KeyRange  # 
 from .store import (ArrayIndexOutOfBoundsException, DataStore, DeviceBatch, DeviceKeys,  # noqa: F401
                     DistMLException, DMatrix,
                     IllegalArgumentException, IllegalStateException, Model, NativeError,
-                    encode_array_push, encode_matrix_push, pinned_empty)
+                    encode_array_push, encode_matrix_push, pack_push_device, pinned_empty, record_bytes,
+                    unpack_fetch_device)
 
 __version__ = "0.1.0"

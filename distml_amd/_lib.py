@@ -102,6 +102,10 @@ SIGNATURES = {
     "dml_prereduce_begin_ctx": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32, _vp, _P(_vp)]),
     "dml_prereduce_verify": (C.c_int, [_vp, _P(_i32)]),
     "dml_shard_split": (C.c_int, [_P(dml_desc), _i32, _i64, _i32, _P(_vp), _P(_i64), _i32, _vp, _i64, _P(_i64), _vp]),
+    "dml_record_bytes": (C.c_int, [_P(dml_desc), _i32, _u32, _P(_i64), _P(_i64)]),
+    "dml_records_pack_device": (C.c_int, [_P(dml_desc), _i32, _u32, _vp, _i64, _i64, _vp, _vp, _i64, _P(_i64), _vp]),
+    "dml_records_unpack_device": (C.c_int, [_P(dml_desc), _i32, _u32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "dml_diag_codec_knob": (C.c_int, [_i32, _i64]),
     "dml_group_unique_id": (C.c_int, [_vp, _i32]),
     "dml_group_push_exchange": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
     "dml_group_push_moments": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
@@ -160,6 +164,11 @@ DML_PULL_REQUEST_ORDER = 0x1
 DML_PULL_MAX_WORLD = 64
 DML_PULL_WAVE_BYTES = 1024
 DML_PULL_BLOCK_BYTES = 4096
+# the record codec: k_rec_pack / k_rec_unpack's tile, and dml_diag_codec_knob
+DML_CODEC_WAVE_BYTES = 1024
+DML_CODEC_BLOCK_BYTES = 4096
+DML_CODEC_KNOB_WIDE_INDEX = 1
+DML_CODEC_KNOB_LOADS = 2
 
 
 class NativeLibraryMissing(RuntimeError):

@@ -442,11 +442,7 @@ class DataStore:
                                            "(PSAgent passes the server-side format, PSAgent.java:279)")
 
     def _fetch_record_bytes(self) -> int:
-        f = self.format
-        if f.dataType == DataDesc.DATA_TYPE_MATRIX:
-            return f.keySize + self._cols * (8 if f.adaGrad and f.valueType == DataDesc.ELEMENT_TYPE_FLOAT
-                                             else f.valueSize)
-        return f.keySize + (8 if f.valueType == DataDesc.ELEMENT_TYPE_FLOAT else f.valueSize)
+        return record_bytes(self.format, self._cols)[1]
 
     # ---- factory (DataStore.java:41-92) -------------------------------------
     @staticmethod
@@ -555,3 +551,48 @@ def encode_array_push(keys, values, key_type: int, value_type: int, value_stride
     v = np.asarray(values, dtype=np.dtype(dt).newbyteorder("<"))
     out[:, K:K + v.itemsize] = v.view(np.uint8).reshape(len(keys), v.itemsize)
     return out.tobytes()
+
+
+# ---- the same codec on the device (dml_records_pack_device / _unpack_device) --------
+def record_bytes(format: DataDesc, cols: int, flags: int = 0):
+    """(push record bytes, fetch record bytes) of a store of this format (dml_record_bytes).
+    `flags`: DML_FLAG_FLOAT_ARRAY_REF_STRIDE as the store was created with."""
+    push, fetch = C.c_int64(), C.c_int64()
+    check(_lib.load().dml_record_bytes(C.byref(format.to_c()), int(cols), int(flags), C.byref(push), C.byref(fetch)))
+    return push.value, fetch.value
+
+
+def pack_push_device(format: DataDesc, cols: int, keys, values_ptr: int, n: int, out_ptr: int, cap: int,
+                     stream: Optional[int] = None, flags: int = 0) -> int:
+    """encode_matrix_push / encode_array_push on the device: `n` push records written at
+    `out_ptr` (4-byte aligned, `cap` bytes) from the row-major T[n][cols] at `values_ptr`;
+    returns the byte count. `keys` is a DeviceKeys of n keys, or an int key_lo (record j
+    gets key_lo + j). `stream` is a raw hipStream_t: the call enqueues there and returns,
+    and the caller synchronises it before handing the records to pushDevice (a push reads
+    its buffers from the store's own streams). None: synchronous."""
+    out_len = C.c_int64()
+    if isinstance(keys, DeviceKeys):
+        if keys.n != n:
+            raise ValueError("pack_push_device: keys.n differs from n")
+        kptr, key_lo = keys.ptr, 0
+    else:
+        kptr, key_lo = 0, int(keys)
+    check(_lib.load().dml_records_pack_device(C.byref(format.to_c()), int(cols), int(flags), C.c_void_p(kptr or None),
+                                              key_lo, int(n), C.c_void_p(values_ptr or None),
+                                              C.c_void_p(out_ptr or None), int(cap), C.byref(out_len),
+                                              C.c_void_p(stream or None)))
+    return out_len.value
+
+
+def unpack_fetch_device(format: DataDesc, cols: int, records_ptr: int, n: int, values_ptr: Optional[int],
+                        alpha_ptr: Optional[int] = None, keys_ptr: Optional[int] = None,
+                        stream: Optional[int] = None, flags: int = 0) -> None:
+    """The inverse of handleFetchDevice's layout, on the device: the `n` fetched records at
+    `records_ptr` into T[n][cols] at `values_ptr`, AdaGrad's float[n][cols] alphas at
+    `alpha_ptr` and int64[n] keys (8-byte aligned) at `keys_ptr`; a plane whose pointer is
+    None is skipped. `stream` as in pack_push_device; the records must be complete in its
+    order (a handleFetchDevice given the same stream is)."""
+    check(_lib.load().dml_records_unpack_device(C.byref(format.to_c()), int(cols), int(flags),
+                                                C.c_void_p(records_ptr or None), int(n), C.c_void_p(keys_ptr or None),
+                                                C.c_void_p(values_ptr or None), C.c_void_p(alpha_ptr or None),
+                                                C.c_void_p(stream or None)))

@@ -589,6 +589,81 @@ int dml_shard_split(const dml_desc* desc, int32_t cols, int64_t total_rows, int3
                     const void* const* dev_bufs, const int64_t* lens, int32_t n, void* dev_out,
                     int64_t out_cap, int64_t* counts, void* stream);
 
+/* --- device record codec (the client's writeMap / readMap, in HBM) ------- */
+
+/* The worker's side of the wire format, for tensors that are already in device memory:
+ * SparseMatrix.writeMap / SparseArray.writeMap (SparseMatrix.java:96-148,
+ * SparseArray.java:63-76) and the readMap that follows every fetch. Store-less, like
+ * dml_shard_split: `desc` (and `cols` for matrices; arrays ignore it and use 1) names the
+ * layout, the calls run on the current device and launch their kernels on `stream`.
+ * `flags`: DML_FLAG_FLOAT_ARRAY_REF_STRIDE as the store was created with; the other
+ * DML_FLAG_* bits are accepted and mean nothing here; any other bit is DML_E_INVALID_ARG.
+ *
+ * Record bytes (dml_record_bytes; either out-pointer may be NULL):
+ *   push   matrices (AdaGrad included) [K key LE][cols x V LE]; arrays [K][V], a float
+ *          array under DML_FLAG_FLOAT_ARRAY_REF_STRIDE [K][f32][4 zero bytes]
+ *   fetch  what dml_store_fetch_device, _fetch_range_device and dml_group_pull write: the
+ *          push layout for plain matrices and int / double arrays; AdaGrad
+ *          [K][cols x (f32 value, f32 alpha)]; FloatArrayStore [K][f32][4 pad], under
+ *          either flag
+ *
+ * dml_records_pack_device writes n push records at dev_out: record j holds key
+ * dev_keys[j], or key_lo + j when dev_keys is NULL (a full-range gradient needs no key
+ * list), and row j of dev_values, a row-major contiguous T[n][cols]. A 4-byte key is the
+ * low 4 bytes of the int64 (the writer's (int) cast). *out_len = n x push record bytes.
+ *
+ * dml_records_unpack_device reads n fetch records at dev_records and writes up to three
+ * planes, each skipped when its pointer is NULL (all three NULL: DML_E_INVALID_ARG):
+ * dev_values_out T[n][cols]; dev_alpha_out float[n][cols], AdaGrad descs only (non-NULL
+ * for any other desc: DML_E_INVALID_ARG); dev_keys_out int64[n], a 4-byte key
+ * sign-extended as DataDesc.readKey does.
+ *
+ * Every move is a dword move: no float instruction touches a value, so NaN payloads,
+ * -0.0 and denormals pass unchanged. Key arrays are 8-byte aligned; every other device
+ * pointer (values, records, output, planes, f64 ones included) is 4-byte aligned and
+ * nothing more, the rule of device pushes and fetch outputs. Only
+ * [dev_out, dev_out + *out_len) is ever written, and of each plane exactly its
+ * n x cols x V bytes (n x 8 for keys), so outputs may lie between other live data.
+ * Inputs are read only inside their n records / rows / keys.
+ *
+ * Ordering: stream == NULL launches and waits; otherwise the kernels are enqueued on
+ * `stream` and the call returns. Two consequences: (1) the inputs must be complete in
+ * `stream` order (written by earlier work on `stream`, or by work the caller has
+ * ordered before it; a dml_store_fetch_device given the same `stream` is); (2) a push
+ * call reads its buffers from the store's own streams, not from `stream`, so the
+ * caller synchronises `stream` before it hands a packed buffer to
+ * dml_store_push_batch_device or a dml_group_push_* call.
+ *
+ * Errors, all before any launch and with nothing written. DML_E_INVALID_ARG: a null
+ * desc or out_len, n < 0, matrix cols <= 0, a null required pointer with n > 0
+ * (dev_values, dev_out; dev_records), a misaligned pointer, an unknown flag bit, an
+ * output that overlaps an input of the same call or another output. DML_E_BAD_DESC: a
+ * desc no store has. DML_E_UNSUPPORTED: a matrix desc with dense_column == 0 (SURVEY
+ * defect 3), or a record of 2^31 dwords and more. DML_E_CAPACITY: cap < n x push record
+ * bytes. *out_len is n x push record bytes whenever desc, cols, flags and n are valid
+ * (so after DML_E_CAPACITY it says what was needed), else 0. n == 0 is DML_OK with
+ * *out_len = 0 and nothing launched. */
+int dml_record_bytes(const dml_desc* desc, int32_t cols, uint32_t flags, int64_t* push_rec, int64_t* fetch_rec);
+int dml_records_pack_device(const dml_desc* desc, int32_t cols, uint32_t flags, const int64_t* dev_keys,
+                            int64_t key_lo, int64_t n, const void* dev_values, void* dev_out, int64_t cap,
+                            int64_t* out_len, void* stream);
+int dml_records_unpack_device(const dml_desc* desc, int32_t cols, uint32_t flags, const void* dev_records,
+                              int64_t n, int64_t* dev_keys_out, void* dev_values_out, float* dev_alpha_out,
+                              void* stream);
+/* Output bytes of one wave instruction's 64 lines and of one block's tile in the codec's
+ * kernels (k_rec_pack, k_rec_unpack): the sizes their tests place stream and plane ends at. */
+#define DML_CODEC_WAVE_BYTES 1024
+#define DML_CODEC_BLOCK_BYTES 4096
+/* Codec knob (diagnostic / tests / timing; process-wide, read at every launch; the bytes
+ * are the same for every value). DML_CODEC_KNOB_WIDE_INDEX 1: a line's record or row by
+ * 64-bit division whatever the length (the path streams of 2^32 dwords and more take;
+ * shorter ones divide in 32 bits). DML_CODEC_KNOB_LOADS: 0 = source loads chosen by record
+ * length, 1 = every dword gathered singly, 2 = 16-byte loads wherever a line lies inside
+ * one row. DML_E_INVALID_ARG for an unknown knob or value. */
+#define DML_CODEC_KNOB_WIDE_INDEX 1
+#define DML_CODEC_KNOB_LOADS 2
+int dml_diag_codec_knob(int32_t knob, int64_t value);
+
 /* --- native multi-GPU shard group (RCCL) -------------------------------- *
  * One process per GPU; rank r owns shard r of KeyRange.linearSplit(world)
  * (KeyRange.java:68-80). Full-range device-resident pushes are pre-reduced in
