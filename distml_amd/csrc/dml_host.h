@@ -1,4 +1,4 @@
-// dml_host.h — what the host translation units of the C-ABI share (dml_store.hip,
+// dml_host.h — what the host translation units of the C-ABI share (dml_store*.hip,
 // dml_prereduce.hip, dml_group.hip). Host only; the types the kernels see are in
 // dml_internal.h. Not part of the public ABI.
 #pragma once
