@@ -35,7 +35,19 @@ class dml_store_counters(C.Structure):
     _fields_ = [("chunks", C.c_int64), ("spec_chunks", C.c_int64), ("spec_reruns", C.c_int64),
                 ("identity_pushes", C.c_int64), ("reused_pushes", C.c_int64), ("indexed_pushes", C.c_int64),
                 ("sparse_big_chunks", C.c_int64), ("sparse_replays", C.c_int64),
-                ("ident_launches", C.c_int64)]
+                ("ident_launches", C.c_int64), ("sparse_counted_chunks", C.c_int64)]
+
+
+# What a pre-reduce context or a group's pre-reduce engine counts (dml_prectx_stats,
+# dml_group_prereduce_stats): sparse_counted_chunks is an array store's counter, which those
+# two calls leave at 0 and their Python mirrors do not report.
+PREREDUCE_COUNTERS = tuple(f for f, _ in dml_store_counters._fields_ if f != "sparse_counted_chunks")
+
+
+class dml_sparse_plan_info(C.Structure):
+    """Mirror of dml_sparse_plan_info (dml_diag_sparse_plan)."""
+    _fields_ = [(n, C.c_int64) for n in ("nrec", "nleaves", "nbig", "cap1", "cap2", "capS")] + \
+               [(n, C.c_int32) for n in ("SL", "D2", "nbins1", "compact", "big", "BL", "bshift", "reserved")]
 
 
 # Every symbol include/distml_ps.h declares, with its ctypes signature.
@@ -132,6 +144,7 @@ SIGNATURES = {
     "dml_diag_gather_floor": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _P(C.c_float)]),
     "dml_diag_dense_floor": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _P(C.c_float), _P(_i32)]),
     "dml_diag_store_knob": (C.c_int, [_vp, _i32, _i64]),
+    "dml_diag_sparse_plan": (C.c_int, [_i32, _i64, _P(_i64), _i32, _i32, _P(dml_sparse_plan_info)]),
     "dml_last_error": (C.c_char_p, []),
     "dml_version": (C.c_char_p, []),
 }

@@ -329,6 +329,15 @@ SpPlan sparse_plan(const Batch& bt, int nb, int64_t rows);
 // The one-level partition where it applies (compact fp32 plan, >= 8 pushes balanced
 // over the slices, big leaves of 2 K - 8.7 K records on average): sets pl.big.
 void sparse_plan_big(SpPlan& pl, const Batch& bt, int64_t rows);
+// One 8-B word per fp32 record through the partition (SpPlan::compact): the row within
+// its level-1 bin fits the word, and no ragged tail (compact words carry no sequence to
+// cut at). Decided between sparse_plan and sparse_plan_big.
+bool sparse_compact_ok(int vtype, const SpPlan& pl, bool has_tail_cut);
+// Line buckets of the leaf kernels, bucket = (row - leaf's first row) >> bshift: the
+// smallest shift that fits a leaf of 2^SL rows into k_sp_leaf's buckets, a big leaf of
+// 2^BL rows into k_sp_leaf_big's.
+int sparse_leaf_bshift(int SL);
+int sparse_big_bshift(int BL);
 hipError_t launch_sparse_partition_big(const Batch& bt, const SpPlan& pl, const SpLayout& l, uint8_t* ws,
                                        int64_t stride, int K, int64_t first, int64_t rows, Ctrl* ctrl,
                                        uint64_t tail_cut, SpStat* hstat, hipStream_t st);

@@ -1078,6 +1078,22 @@ void sparse_plan_big(SpPlan& pl, const Batch& bt, int64_t rows) {
     pl.big = 1;
 }
 
+bool sparse_compact_ok(int vtype, const SpPlan& pl, bool has_tail_cut) {
+    return vtype == kF32 && pl.SL + pl.D2 <= kSpCompactRowBits && !has_tail_cut;
+}
+
+int sparse_leaf_bshift(int SL) {
+    int bshift = 0;  // line buckets: leaf rows >> bshift < kSpLines
+    while ((((int64_t)1 << SL) >> bshift) > kSpLines) ++bshift;
+    return bshift;
+}
+
+int sparse_big_bshift(int BL) {
+    int bshift = 0;  // kSpBigLines line buckets over the big leaf's rows
+    while ((((int64_t)1 << BL) >> bshift) > kSpBigLines) ++bshift;
+    return bshift;
+}
+
 uint32_t sparse_seq_cut(const SpPlan& pl, const Batch& bt, uint64_t cut, int64_t stride) {
     if (cut == kNoPos) return kSpSkip;
     const int gb = (int)(cut >> 40);
@@ -1278,8 +1294,7 @@ hipError_t launch_sparse_leaf(int vtype, void* shard, const SpPlan& pl, const Sp
     if (pl.big) {
         if (vtype != kF32) return hipErrorInvalidValue;
         g_kernel_name = "dml::k_sp_leaf_big";
-        int bshift = 0;  // kSpBigLines line buckets over the big leaf's rows
-        while ((((int64_t)1 << pl.BL) >> bshift) > kSpBigLines) ++bshift;
+        const int bshift = sparse_big_bshift(pl.BL);
         hipExtLaunchKernelGGL(k_sp_leaf_big, dim3((unsigned)pl.nbig), dim3(kSpBigThreads), 0, st, ev.start, ev.stop, 0,
                               (float*)shard, (const uint32_t*)(ws + l.curS), pl.nbig, pl.capS,
                               (const uint64_t*)(ws + l.big), pl.BL, bshift, ws + l.leafflag, ctrl, prev);
@@ -1291,9 +1306,7 @@ hipError_t launch_sparse_leaf(int vtype, void* shard, const SpPlan& pl, const Sp
     const uint64_t* comp2 = (const uint64_t*)(ws + l.comp2);
     uint8_t* flag = ws + l.leafflag;
     const dim3 grid((unsigned)pl.nleaves);
-    // line buckets: leaf rows >> bshift < kSpLines
-    int bshift = 0;
-    while ((((int64_t)1 << pl.SL) >> bshift) > kSpLines) ++bshift;
+    const int bshift = sparse_leaf_bshift(pl.SL);
     g_kernel_name = vtype == kF64   ? "dml::k_sp_leaf<double, false>"
                     : vtype == kI32 ? "dml::k_sp_leaf<int, false>"
                     : pl.compact    ? "dml::k_sp_leaf<float, true>"

@@ -248,7 +248,7 @@ int launch_chunk(dml_store* s, Chunk& c, Workspace& W, const Ctrl* prev) {
         {
             c.sp = sparse_plan(c.bt, c.nb, s->rows);
             // one 8-B word per fp32 record through the partition
-            c.sp.compact = vt == kF32 && c.sp.SL + c.sp.D2 <= kSpCompactRowBits && c.tail_cut == kNoPos;
+            c.sp.compact = sparse_compact_ok(vt, c.sp, c.tail_cut != kNoPos);
             // big leaves sorted in LDS where they apply: no second partition pass (§4)
             sparse_plan_big(c.sp, c.bt, s->rows);
             c.spl = sparse_layout(c.sp, s->V);
@@ -461,6 +461,7 @@ int retire_front(dml_store* s) {
     W.clean = s->is_matrix && !abnormal && W.clears;
     s->st.chunks += 1;
     if (!s->is_matrix && c.sp.big) s->st.sparse_big_chunks += 1;
+    if (!s->is_matrix && !c.sp.fast) s->st.sparse_counted_chunks += 1;  // launch_chunk fell back
     if (c.spec && ctl.spec_ok != 0u) {
         std::swap(s->data, s->data_alt);  // every identity record verified: the output is the shard
         s->st.spec_chunks += 1;

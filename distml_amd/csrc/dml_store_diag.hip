@@ -192,6 +192,40 @@ int dml_diag_store_knob(dml_store* s, int32_t knob, int64_t value) {
     }
 }
 
+// launch_chunk's plan for an array chunk, by the functions launch_chunk and
+// launch_sparse_leaf call, in their order; nothing here touches a device.
+int dml_diag_sparse_plan(int32_t value_type, int64_t rows, const int64_t* nrecs, int32_t n, int32_t tail_cut,
+                         dml_sparse_plan_info* out) {
+    if (!nrecs || !out || n < 1 || n > kMaxW || rows < 1 || rows > INT32_MAX ||
+        (value_type != kI32 && value_type != kF32 && value_type != kF64))
+        return set_err(DML_E_INVALID_ARG, "bad sparse plan arguments");
+    Batch bt{};
+    for (int b = 0; b < n; ++b) {
+        if (nrecs[b] < 0) return set_err(DML_E_INVALID_ARG, "negative record count");
+        bt.nrec[b] = nrecs[b];
+    }
+    SpPlan pl = sparse_plan(bt, n, rows);
+    pl.compact = sparse_compact_ok(value_type, pl, tail_cut != 0);
+    sparse_plan_big(pl, bt, rows);
+    *out = dml_sparse_plan_info{};
+    out->nrec = pl.nrec;
+    out->nleaves = pl.nleaves;
+    out->cap1 = pl.cap1;
+    out->cap2 = pl.cap2;
+    out->SL = pl.SL;
+    out->D2 = pl.D2;
+    out->nbins1 = pl.nbins1;
+    out->compact = pl.compact;
+    out->big = pl.big;
+    if (pl.big) {
+        out->BL = pl.BL;
+        out->nbig = pl.nbig;
+        out->capS = pl.capS;
+    }
+    out->bshift = pl.big ? sparse_big_bshift(pl.BL) : sparse_leaf_bshift(pl.SL);
+    return DML_OK;
+}
+
 int dml_store_kernel_name(dml_store* s, char* out, int32_t cap) {
     if (int rc = check_store(s)) return rc;
     if (!out || cap <= 0) return set_err(DML_E_INVALID_ARG, "bad name buffer");

@@ -150,7 +150,7 @@ class HipOps:
     def ctx_stats(self, ctx, reset: bool = False) -> dict:
         c = _lib.dml_store_counters()
         check(_lib.load().dml_prectx_stats(C.c_void_p(ctx), C.byref(c), int(reset)))
-        return {f: getattr(c, f) for f, _ in c._fields_}
+        return {f: getattr(c, f) for f in _lib.PREREDUCE_COUNTERS}
 
     def begin_ctx(self, ctx, dev_ptrs, lens, stream: int):
         n = len(dev_ptrs)
@@ -813,7 +813,7 @@ class NativeShardGroup:
     def prereduce_stats(self, reset: bool = False) -> dict:
         c = _lib.dml_store_counters()
         check(self._L.dml_group_prereduce_stats(C.c_void_p(self._h), C.byref(c), int(reset)))
-        return {f: getattr(c, f) for f, _ in c._fields_}
+        return {f: getattr(c, f) for f in _lib.PREREDUCE_COUNTERS}
 
     def close(self) -> None:
         if self._h:

@@ -161,6 +161,10 @@ typedef struct dml_store_counters {
     int64_t sparse_replays;     /* array chunks with leaves the exact replay applied */
     int64_t ident_launches;     /* chunks / pre-reduce pieces launched through the all-identity
                                    kernels (k_flat_ident, k_ada_ident) */
+    int64_t sparse_counted_chunks; /* array chunks whose apply read the counted partition's layout: a
+                                   bin, leaf or slice region of the single-pass partition overflowed,
+                                   or compact records met a cutoff. 0 from
+                                   dml_prectx_stats and dml_group_prereduce_stats */
 } dml_store_counters;
 int dml_store_stats(dml_store* s, dml_store_counters* out, int32_t reset);
 
@@ -957,6 +961,22 @@ int dml_diag_pull_kernels(const int64_t* dev_keys, int64_t nkeys, int64_t total_
  * 2048 / 4096: one / four vectors per thread); the bytes are the same for every value. */
 #define DML_KNOB_FETCH_KERNEL 3
 int dml_diag_store_knob(dml_store* s, int32_t knob, int64_t value);
+
+/* The partition plan an array store makes for one chunk before any kernel runs (diagnostic /
+ * tests; host arithmetic only, no device call, works without a GPU): value_type is the store's
+ * DML_ELEMENT_TYPE_*, rows its shard's size, nrecs[0..n) the records of each of the chunk's
+ * pushes (1 <= n <= 64), tail_cut != 0 when some push of the chunk ends inside a record. The
+ * fields are SpPlan's: leaves of 2^SL rows, 2^D2 leaves per level-1 bin, cap1 /
+ * cap2 records per bin / leaf of the single-pass layout, compact = 8-byte fp32 words, big = the
+ * one-level partition with nbig big leaves of 2^BL rows and capS records per (big leaf, slice);
+ * BL, nbig and capS are 0 unless big. bshift: the launched leaf kernel's line bucket is
+ * (row - leaf's first row) >> bshift. Returns DML_E_INVALID_ARG for a bad argument. */
+typedef struct dml_sparse_plan_info {
+    int64_t nrec, nleaves, nbig, cap1, cap2, capS;
+    int32_t SL, D2, nbins1, compact, big, BL, bshift, reserved;
+} dml_sparse_plan_info;
+int dml_diag_sparse_plan(int32_t value_type, int64_t rows, const int64_t* nrecs, int32_t n, int32_t tail_cut,
+                         dml_sparse_plan_info* out);
 
 /* --- misc --------------------------------------------------------------- */
 const char* dml_last_error(void);   /* thread-local message for the last failure */

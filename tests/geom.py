@@ -410,11 +410,14 @@ def full_range_case(oracle, rows=1000, cols=256, W=5):
     return host, o
 
 
-# The sparse one-level partition (k_sp_leaf_big) at the smallest shard that reaches it
-# with pushes that list each key once: sparse_plan_big wants >= 8 pushes and a mean of
-# >= kSpBigCap / 6 = 682 records per big leaf, with at most kSpBigBins = 16 384 big
-# leaves, so >= 11.2 M records; 64 pushes (one chunk) then need >= 174 592 distinct keys
-# each, so > 8 x 16 384 rows: 262 144 rows (big leaves of 16 rows), 64 x 180 000 keys.
+# The sparse one-level partition (k_sp_leaf_big) on packed records, with pushes that list each key
+# once: sparse_plan_big wants >= 8 pushes and a mean of >= kSpBigCap / 6 = 682 records per big
+# leaf. With kSpBigBins = 16 384 big leaves that is >= 11.2 M records, and 64 pushes (one chunk)
+# then need >= 174 592 distinct keys each, so > 8 x 16 384 rows: 262 144 rows (big leaves of 16
+# rows), 64 x 180 000 keys. This is not the smallest such shard: the route model
+# (tests/sparse_route.py) finds 131 073 rows, still big leaves of 16 rows but only 8 193 of them,
+# so 5.59 M records; tests/sparse_cases.py's big cases use 8 193 big leaves too. The shape stays
+# as it is: it is the one with every big leaf the histogram can hold.
 BIG_LEAF = dict(first=5, rows=262_144, n=64, per=180_000)
 
 

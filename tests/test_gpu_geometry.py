@@ -24,6 +24,7 @@ import pytest
 
 import geom
 import kat
+import sparse_route
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +85,16 @@ def run_case(oracle, case, lead, separated=False):
         if case.get("spec"):
             st = s.stats()
             assert st["chunks"] == calls and st["spec_chunks"] == case["spec"], st
+        if case["kind"] == "sparse":
+            # the route tests/sparse_route.py derives from the same bytes: single pass; the fp32
+            # cases' repeated key sends one leaf through the compact replay (branch 2)
+            if "route" not in ref:
+                ref["route"] = sparse_route.call_routes(case["vt"], case["kt"], case["first"], case["rows"],
+                                                        ref["pushes"])
+            want, kname = sparse_route.expect(ref["route"])
+            st = s.stats()
+            assert {k: st[k] for k in want} == want and name == kname, (st, want, name, kname)
+            assert want == dict(sparse_big_chunks=0, sparse_counted_chunks=0, sparse_replays=int(case["vt"] == 1))
         a.check()
     finally:
         s.close()
@@ -167,6 +178,7 @@ def test_sparse_big_leaf_packed(oracle, place):
         st = s.stats()
         assert s.error_state()[0] == 0
         assert st["sparse_big_chunks"] == 1 and st["sparse_replays"] == 0, st
+        assert st["sparse_counted_chunks"] == 0, st  # no (big leaf, slice) region overflowed
         geom.kernel_is(s.kernel_name(), "k_sp_leaf_big")
         assert kat.bits_equal(s.values(), want)
         a.check()

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import opseq
+import sparse_route
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +48,7 @@ class _Runner:
             if opseq.flat_shaped(cfg):
                 self.s.set_knob(1, 0)  # DML_KNOB_IDENT_FULL_MIN_BYTES: k_ada_ident at this size
         self.names = set()
+        self.route_lo, self.route_hi = {}, {}  # the sparse counters the calls' bytes plan (arrays)
         self.at = 0     # index of the op being applied
         self.op = None
 
@@ -124,6 +126,23 @@ class _Runner:
             return out
         return None
 
+    def plan_route(self, call, failed):
+        """Array stores: the sparse counters tests/sparse_route.py derives from the call's bytes. A
+        call the oracle applied whole counts exactly; the call that fails counts as an upper bound
+        (its chunks behind the failing one are dropped, and the model does not see which chunk an
+        int32 negative counter is in)."""
+        cfg = self.cfg
+        if cfg["data_type"] != opseq.ARRAY:
+            return
+        routes = sparse_route.call_routes(cfg["value_type"], cfg["key_type"], cfg["first"], cfg["rows"],
+                                          [bytes(p) for p in call["pushes"]], 8 if cfg["ref_stride"] else None)
+        if not routes:
+            return
+        for k, v in sparse_route.expect(routes)[0].items():
+            self.route_hi[k] = self.route_hi.get(k, 0) + v
+            if not failed:
+                self.route_lo[k] = self.route_lo.get(k, 0) + v
+
     def took(self, e, want_err, raised):
         """A store exception is legal only once the oracle has failed in this burst; anything
         that is not one of the reference's three push errors (a HIP error, say) goes up as it is."""
@@ -145,6 +164,7 @@ class _Runner:
                 if want_err is None:
                     assert call["applied"]
                     want_err = side.push_call(call)
+                    self.plan_route(call, failed=want_err is not None)
                 dev = [torch.from_numpy(p).cuda() for p in call["pushes"]]
                 keep.append(dev)  # alive to the end of the burst
                 torch.cuda.synchronize()
@@ -212,6 +232,9 @@ def test_sequence_matches_oracle(oracle, name, seed):
             assert reached[path] >= need, (path, reached[path], need, st, sorted(r.names))
         if not opseq.spec_shaped(cfg):
             assert st["spec_chunks"] == 0, st
+        # array stores: every applied call took the route the model derives from its bytes
+        for k, hi in r.route_hi.items():
+            assert r.route_lo.get(k, 0) <= st[k] <= hi, (k, r.route_lo.get(k, 0), st[k], hi)
     finally:
         r.close()
 

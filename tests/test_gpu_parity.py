@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import kat
+import sparse_route
 
 pytestmark = pytest.mark.gpu
 
@@ -41,6 +42,24 @@ def mk_store(case_or_desc, first=None, last=None, cols=1, ref_stride=False, asyn
 def oracle_store(oracle, fmt, first, last, cols=1, ref_stride=False):
     return oracle.OracleStore(fmt.dataType, fmt.keyType, fmt.valueType, first, last, cols,
                               int(fmt.denseColumn), int(fmt.adaGrad), int(ref_stride))
+
+
+def assert_sparse_route(s, fmt, first, rows, calls, value_stride=None, **declared):
+    """The array store `s` (counters reset before the calls) took the route tests/sparse_route.py
+    derives from the calls' own bytes: the three sparse counters and the leaf kernel's name. `calls`:
+    one list of encoded pushes per push call; declared: what the test's docstring says about the
+    first chunk (big / counted / flagged / branch), checked against the model too."""
+    routes = [r for c in calls for r in sparse_route.call_routes(fmt.valueType, fmt.keyType, first, rows, c,
+                                                                 value_stride)]
+    want, name = sparse_route.expect(routes)
+    st = s.stats()
+    assert {k: st[k] for k in want} == want, (st, want)
+    assert s.kernel_name() == name, (s.kernel_name(), name)
+    r = routes[0]
+    got = dict(big=r["big"], counted=tuple(sorted(r["why"])), branch=r["replay_branch"],
+               flagged=tuple(sorted({k for v in r["flagged"].values() for k, _ in v})))
+    for k, v in declared.items():
+        assert got[k] == v, (k, got)
 
 
 # --------------------------------------------------------------------------- KATs
@@ -160,16 +179,22 @@ def test_array_random_parity(oracle, value_type, key_type, ref_stride):
         pushes.append(encode_array_push(first + k, v, key_type, value_type, value_stride=vs))
     for p in pushes:
         assert o.push(p) == 0
+    s.stats(reset=True)
     s.handlePushBatch(fmt, pushes)
     assert kat.bits_equal(s.values(), o.data)
+    # typical keys: the single-pass partition, nothing counted, flagged or replayed
+    assert_sparse_route(s, fmt, first, rows, [pushes], value_stride=vs, big=False, counted=(), branch=None)
 
 
 @pytest.mark.parametrize("value_type,api", [(1, "batch"), (3, "batch"), (1, "sequential")])
 def test_array_repeated_keys_in_push_exact(oracle, value_type, api):
     """A push that lists a key several times (never produced by SparseArray.writeMap, but
-    legal bytes): the reference adds the repeats in record order. The ordered sparse path
-    sorts (row, sequence) per leaf, so the result is bit-exact; per-push float atomics
-    would not fix the order of the repeats."""
+    legal bytes): the reference adds the repeats in record order. 30 000 records on 3 000 of the
+    50 000 rows overfill the leaves that hold them (cap2, then kSpLeafCap): every chunk falls back
+    to the counted partition and its flagged leaves take sparse_replay's counted branch (4), which
+    sorts (row, sequence), so the result is bit-exact; per-push float atomics would not fix the
+    order of the repeats. (The repeats inside a leaf the LDS sort applies are
+    tests/test_gpu_sparse_edges.py's bucket cases.)"""
     from distml_amd import DataDesc, encode_array_push
     rng = np.random.default_rng(40 + value_type)
     first, rows = 0, 50_000
@@ -186,19 +211,24 @@ def test_array_repeated_keys_in_push_exact(oracle, value_type, api):
         pushes.append(encode_array_push(first + k, v, 1, value_type))
     for p in pushes:
         assert o.push(p) == 0
+    s.stats(reset=True)
     if api == "batch":
         s.handlePushBatch(fmt, pushes)
     else:
         for p in pushes:
             s.handlePush(fmt, p)
     assert kat.bits_equal(s.values(), o.data)
+    assert_sparse_route(s, fmt, first, rows, [pushes] if api == "batch" else [[p] for p in pushes],
+                        counted=("cap2",), flagged=("records",), branch=4)
     s.close()
 
 
 @pytest.mark.parametrize("value_type", [1, 3])
 def test_array_skewed_leaf_replay_exact(oracle, value_type):
-    """One key range holds far more records than a leaf sorts in LDS (2048): the leaf
-    kernel flags it and the host replays it from a full device sort, exactly."""
+    """One key range holds far more records than a leaf sorts in LDS (2048): 24 000 records on 64
+    keys overflow the single-pass partition's leaf region first (cap2), so the chunk runs the
+    counted partition, whose leaf kernel flags the leaf, and the host replays it from a full
+    device sort of the kept records (sparse_replay's counted branch, 4), exactly."""
     from distml_amd import DataDesc, encode_array_push
     rng = np.random.default_rng(7 + value_type)
     first, rows = 10, 1_000_000
@@ -217,8 +247,10 @@ def test_array_skewed_leaf_replay_exact(oracle, value_type):
         pushes.append(encode_array_push(first + k, v, 0, value_type))
     for p in pushes:
         assert o.push(p) == 0
+    s.stats(reset=True)
     s.handlePushBatch(fmt, pushes)
     assert kat.bits_equal(s.values(), o.data)
+    assert_sparse_route(s, fmt, first, rows, [pushes], counted=("cap2",), flagged=("records",), branch=4)
     # and a following batch after the replay (pipeline state intact)
     more = [encode_array_push(first + rng.choice(rows, 5_000, replace=False), rng.standard_normal(5_000), 0,
                               value_type) for _ in range(3)]
@@ -1519,6 +1551,13 @@ def test_int_array_repeated_keys_exact_error_state(oracle, case):
         else:
             s.handlePushBatch(fmt, pushes) if api == "batch" else [s.handlePush(fmt, p) for p in pushes]
         assert kat.bits_equal(s.values(), o.data)
+        # 10 000 records on 400 keys: as one chunk they overfill two leaves past kSpLeafCap (cap2,
+        # counted, replay branch 4); push by push only cap2 overflows (counted, no replay)
+        if api == "batch":
+            assert_sparse_route(s, fmt, first, rows, [pushes], counted=("cap2",), flagged=("records",), branch=4)
+        elif not rc:
+            calls = [[p] for p in pushes] if api == "sequential" else [pushes[i:i + 2] for i in range(0, 5, 2)]
+            assert_sparse_route(s, fmt, first, rows, calls, counted=("cap2",))
         s.close()
 
 
@@ -1938,11 +1977,16 @@ def test_adagrad_maxdelta_pending_behind_repeated_row(oracle):
 def test_sparse_single_pass_partition_exact(oracle, case):
     """The single-pass sparse partition (fixed-capacity bins, atomic cursors; DESIGN.md
     §4) against the oracle, bit-exact, where it must fall back or cut: `hot_line` — 40
-    pushes all list keys 777..778 (one 32-row line bucket of a leaf holds > 64
-    records): the leaf kernel flags the leaf and the packed exact replay applies it;
-    `cutoff` — a key outside the shard in the middle of push 3: records from it on
-    are not applied (the sequence cut), error state as the reference's;
-    `truncated` — the last push ends inside a record; `push_repeat` — push 2 lists
+    pushes all list keys 777 and 778: chains of 40 adds on two rows. (Leaves of 2^11 rows have
+    2-row line buckets, so the two rows lie in different buckets and neither holds > 64
+    records; what flags a leaf here is a push whose random keys repeat one of its others, and
+    the replay is the compact one, branch 2. The bucket limit itself, 64 against 65, and the
+    packed replay, branch 3, are tests/test_gpu_sparse_edges.py's bucket cases.)
+    `cutoff` — a key outside the shard in the middle of push 3: compact fp32 words carry no
+    sequence to cut at, so the chunk runs the counted partition, records from the key on
+    are not applied, error state as the reference's;
+    `truncated` — the last push ends inside a record (full fp32 records through the single
+    pass); `push_repeat` — push 2 lists
     one key twice (fp32 compact records order a row's adds by push only, so the leaf
     goes to the replay, which re-partitions with full sequence numbers); `f64` —
     DoubleArrayStore (full records) with cross-push repeats only."""
@@ -1979,6 +2023,7 @@ def test_sparse_single_pass_partition_exact(oracle, case):
         if rc:
             err = o.error()
             break
+    s.stats(reset=True)
     if err is None:
         s.handlePushBatch(fmt, pushes)
     else:
@@ -1986,6 +2031,12 @@ def test_sparse_single_pass_partition_exact(oracle, case):
             s.handlePushBatch(fmt, pushes)
         assert (ei.value.code, ei.value.key) == (err[0], err[1])
     assert s.values().tobytes() == o.data.tobytes()
+    declared = {"hot_line": dict(counted=(), flagged=("row_twice_in_push",), branch=2),
+                "cutoff": dict(counted=("compact_cut",), branch=None),
+                "truncated": dict(counted=(), branch=None),
+                "push_repeat": dict(counted=(), flagged=("row_twice_in_push",), branch=2),
+                "f64": dict(counted=(), flagged=(), branch=None)}[case]
+    assert_sparse_route(s, fmt, first, rows, [pushes], big=False, **declared)
 
 
 @pytest.mark.parametrize("case", ["random", "lattice", "hot_big_leaf", "repeats", "push_repeat", "cutoff",
@@ -2053,6 +2104,12 @@ def test_sparse_big_leaves_exact(oracle, case):
     big = case not in ("cutoff", "unbalanced")
     assert st["sparse_big_chunks"] == (1 if big else 0), st
     assert st["sparse_replays"] == (1 if case in ("hot_big_leaf", "push_repeat") else 0), st
+    # `cutoff`: the big plan's compact words carry no sequence to cut at, so the chunk is applied
+    # from the counted partition; no other case overflows a region (tests/sparse_route.py gives
+    # these routes for the same bytes; at 32 M records the model is too slow to run here)
+    assert st["sparse_counted_chunks"] == (1 if case == "cutoff" else 0), st
+    assert s.kernel_name() == ("dml::k_sp_leaf_big" if big else "dml::k_sp_leaf<float, false>"
+                               if case == "cutoff" else "dml::k_sp_leaf<float, true>")
 
 
 @pytest.mark.parametrize("cols", [200, 64])
