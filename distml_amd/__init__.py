@@ -6,7 +6,7 @@ reference's DataStore plugin interface over that C-ABI.
 """
 from ._lib import NativeLibraryMissing, load as load_library  # noqa: F401
 from .datadesc import ALL, EMPTY, DataDesc, KeyCollection, KeyList, KeyRange  # noqa: F401
-from .store import (ArrayIndexOutOfBoundsException, DataStore, DeviceBatch, DeviceKeys,  # noqa: F401
+from .store import (ArrayIndexOutOfBoundsException, Coalescer, DataStore, DeviceBatch, DeviceKeys,  # noqa: F401
                     DistMLException, DMatrix,
                     IllegalArgumentException, IllegalStateException, Model, NativeError,
                     encode_array_push, encode_matrix_push, pack_push_device, pinned_empty, record_bytes,

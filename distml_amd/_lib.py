@@ -118,6 +118,10 @@ SIGNATURES = {
     "dml_records_pack_device": (C.c_int, [_P(dml_desc), _i32, _u32, _vp, _i64, _i64, _vp, _vp, _i64, _P(_i64), _vp]),
     "dml_records_unpack_device": (C.c_int, [_P(dml_desc), _i32, _u32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "dml_diag_codec_knob": (C.c_int, [_i32, _i64]),
+    "dml_coalescer_create": (C.c_int, [_i32, _P(_vp)]),
+    "dml_coalescer_destroy": (None, [_vp]),
+    "dml_coalesce_device": (C.c_int, [_vp, _P(dml_desc), _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _P(_i64), _vp]),
+    "dml_diag_coalesce_times": (C.c_int, [_vp, _P(C.c_float)]),
     "dml_group_unique_id": (C.c_int, [_vp, _i32]),
     "dml_group_push_exchange": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
     "dml_group_push_moments": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
@@ -182,6 +186,10 @@ DML_CODEC_WAVE_BYTES = 1024
 DML_CODEC_BLOCK_BYTES = 4096
 DML_CODEC_KNOB_WIDE_INDEX = 1
 DML_CODEC_KNOB_LOADS = 2
+# the coalescer: k_co_heads' keys per block, k_co_sum's index batch and load depth
+DML_COALESCE_BLOCK_KEYS = 1024
+DML_COALESCE_BATCH = 16
+DML_COALESCE_DEPTH = 4
 
 
 class NativeLibraryMissing(RuntimeError):

@@ -596,3 +596,46 @@ def unpack_fetch_device(format: DataDesc, cols: int, records_ptr: int, n: int, v
                                                 C.c_void_p(records_ptr or None), int(n), C.c_void_p(keys_ptr or None),
                                                 C.c_void_p(values_ptr or None), C.c_void_p(alpha_ptr or None),
                                                 C.c_void_p(stream or None)))
+
+
+# ---- the worker's KeyList + HashMap accumulate on the device (dml_coalesce_device) --------
+class Coalescer:
+    """A coalescer context (dml_coalescer): workspace, a pinned count word and one event on
+    `device`. One call is in flight at a time; close() waits for it."""
+
+    def __init__(self, device: int = 0):
+        self._h = C.c_void_p()
+        check(_lib.load().dml_coalescer_create(int(device), C.byref(self._h)))
+        self._fin = weakref.finalize(self, _lib.load().dml_coalescer_destroy, C.c_void_p(self._h.value))
+
+    def run(self, format: DataDesc, cols: int, keys: DeviceKeys, values_ptr: Optional[int],
+            keys_out_ptr: int, values_out_ptr: Optional[int], inverse_ptr: Optional[int], cap_rows: int,
+            stream: Optional[int] = None) -> int:
+        """Occurrences to one row per key: the distinct keys of `keys` ascending at
+        `keys_out_ptr` (int64, 8-byte aligned), at `values_out_ptr` the sum per key of the
+        rows of the T[keys.n][cols] at `values_ptr`, in list order from +0.0, and at
+        `inverse_ptr` (int32[keys.n], or None) each occurrence's place among the distinct
+        keys. `values_ptr` None (then `values_out_ptr` is None too): keys, inverse and count
+        only, the KeyList half before a fetch. Returns m, the number of distinct keys; more
+        than `cap_rows` raises with code DML_E_CAPACITY and nothing written. The call waits
+        once, for m; with a raw hipStream_t `stream` the writing kernels are then enqueued
+        there and the call returns, with None it waits for them too."""
+        m = C.c_int64()
+        check(_lib.load().dml_coalesce_device(self._h, C.byref(format.to_c()), int(cols), C.c_void_p(keys.ptr or None),
+                                              int(keys.n), C.c_void_p(values_ptr or None),
+                                              C.c_void_p(keys_out_ptr or None), C.c_void_p(values_out_ptr or None),
+                                              C.c_void_p(inverse_ptr or None), int(cap_rows), C.byref(m),
+                                              C.c_void_p(stream or None)))
+        return m.value
+
+    def stage_times(self):
+        """(order, heads, sum) HIP-event milliseconds of the last completed run
+        (dml_diag_coalesce_times)."""
+        ms = (C.c_float * 3)()
+        check(_lib.load().dml_diag_coalesce_times(self._h, ms))
+        return tuple(ms)
+
+    def close(self):
+        if self._h:
+            self._fin()
+            self._h = C.c_void_p()

@@ -668,6 +668,72 @@ int dml_records_unpack_device(const dml_desc* desc, int32_t cols, uint32_t flags
 #define DML_CODEC_KNOB_LOADS 2
 int dml_diag_codec_knob(int32_t knob, int64_t value);
 
+/* --- device gradient coalescer (the worker's KeyList + HashMap, in HBM) --- */
+
+/* The reference worker fetches through a KeyList, a HashSet<Long> (KeyList.java:14-19,59-61),
+ * and accumulates its update per key before SparseMatrix.push writes one record per entry
+ * (SparseMatrix.java:46-60,96-148). A worker on the device holds occurrences instead: n keys
+ * with repeats, and one gradient row per occurrence. dml_coalesce_device turns them into the
+ * reference's shape: one row per distinct key. `desc` (and `cols` for matrices; arrays ignore
+ * it and use 1) names the row, as for the codec; an AdaGrad desc is f32.
+ *
+ * Inputs: dev_keys int64[n]; dev_values a row-major contiguous T[n][cols], T from
+ * desc->value_type.
+ * dev_keys_out[0..m): the distinct keys of the list, ascending as signed 64-bit values;
+ *   *out_rows = m. Unique keys in ascending order are the order the codec's pack and the
+ *   store's identity push want.
+ * dev_inverse_out[j] (int32[n], may be NULL): the u with dev_keys_out[u] == dev_keys[j]; a
+ *   worker gathers the rows it pulled for the unique keys back to its occurrences with it.
+ * dev_values_out[u][c] = (((+0.0 + v[j1][c]) + v[j2][c]) + ...) over the occurrences
+ *   j1 < j2 < ... of key u in LIST ORDER. Each add rounds once as IEEE, no FMA and no
+ *   reassociation; int32 adds wrap mod 2^32 and are not checked. Starting from +0.0 makes
+ *   the result what a zero-initialised reference store holds after one handlePush of the
+ *   occurrences as records in list order (FloatMatrixStore.java:200-222). Consequences: a
+ *   lone -0.0 comes out +0.0, and a signalling NaN comes out quiet.
+ * Keys-only mode, the KeyList half, run before the pull: dev_values == NULL requires
+ *   dev_values_out == NULL; unique keys, the inverse and the count are written.
+ *
+ * Key arrays are 8-byte aligned; every other pointer is 4-byte aligned and nothing more, the
+ * rule of device pushes. Only m x 8, m x cols x V and n x 4 bytes are ever written, so
+ * outputs may lie between other live data. Inputs are read only inside their n keys / rows.
+ *
+ * Count and ordering: the host needs m to size the pack or the pull, so the call makes
+ * exactly one host wait, for the count, on a pinned word of the context. With stream != NULL
+ * the kernels that write the outputs are then enqueued on `stream` and the call returns;
+ * with stream == NULL it waits for everything. Inputs must be complete in `stream` order.
+ * One call is in flight per context: the next call (and dml_coalescer_destroy) first waits
+ * for this one's event. The workspace (about 28 bytes per occurrence and the sort's own)
+ * grows on demand and is reused. A context belongs to the device it was created for and is
+ * not thread-safe.
+ *
+ * Errors. All but DML_E_CAPACITY are found before any HIP call and before `c` is
+ * dereferenced, and leave *out_rows as it was. DML_E_INVALID_ARG: null c / desc / out_rows,
+ * n < 0, matrix cols <= 0, a null required pointer with n > 0 (dev_keys, dev_keys_out;
+ * dev_values_out when dev_values is given), a misaligned pointer, dev_values_out without
+ * dev_values, an output (taken as min(n, cap_rows) rows; the inverse as n words) that
+ * overlaps an input or another output. DML_E_BAD_DESC: a desc no store has.
+ * DML_E_UNSUPPORTED: a matrix desc with dense_column == 0 (SURVEY defect 3), n >= 2^31, a
+ * row of 2^31 dwords or more. DML_E_CAPACITY: m > cap_rows; *out_rows = m says what was
+ * needed and NOTHING is written to any output (the writing kernels are launched only after
+ * the host has seen the count). n == 0: DML_OK, *out_rows = 0, nothing launched. */
+typedef struct dml_coalescer dml_coalescer; /* workspace, pinned count word, one event */
+int dml_coalescer_create(int32_t device, dml_coalescer** out);
+void dml_coalescer_destroy(dml_coalescer* c);
+int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32_t cols, const int64_t* dev_keys, int64_t n,
+                        const void* dev_values, int64_t* dev_keys_out, void* dev_values_out,
+                        int32_t* dev_inverse_out, int64_t cap_rows, int64_t* out_rows, void* stream);
+/* The coalescer's tiling, the sizes its tests place edges at: sorted keys per block of
+ * k_co_heads; occurrence indices a group of k_co_sum fetches at a time (a group of fewer
+ * lanes fetches one per lane); rows whose loads it issues before the first add. */
+#define DML_COALESCE_BLOCK_KEYS 1024
+#define DML_COALESCE_BATCH 16
+#define DML_COALESCE_DEPTH 4
+/* Diagnostic / timing: HIP-event times in ms of the last completed dml_coalesce_device on
+ * `c` (waits for it): ms3[0] order (pairs and sort), ms3[1] k_co_heads (count, offsets and
+ * the writing pass; the host wait between them is not counted), ms3[2] the row sum (0 in
+ * keys-only mode). DML_E_INVALID_ARG before the first call that ran to its end. */
+int dml_diag_coalesce_times(dml_coalescer* c, float* ms3);
+
 /* --- native multi-GPU shard group (RCCL) -------------------------------- *
  * One process per GPU; rank r owns shard r of KeyRange.linearSplit(world)
  * (KeyRange.java:68-80). Full-range device-resident pushes are pre-reduced in
