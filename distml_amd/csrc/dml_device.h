@@ -1,6 +1,7 @@
-// dml_device.h — device-side helpers shared by the kernel files (dml_kernels.hip,
-// dml_fetch.hip, dml_sparse.hip): vector load types, wire decode (DataDesc.java:131-192),
-// KeyRange indexOf, IEEE element adds. Not part of the public ABI.
+// dml_device.h — device-side helpers shared by the kernel files: vector load types, wire
+// decode (DataDesc.java:131-192), KeyRange indexOf, IEEE element adds, 16-B pack / unpack,
+// the wave's LDS hand-over, AdaGrad's alpha and the maxDelta candidates. Not part of the
+// public ABI.
 #pragma once
 #include "dml_internal.h"
 
@@ -105,5 +106,99 @@ template <> struct Elem<double> {
     __device__ static double load(const uint8_t* p) { return from_bits(ld32(p), ld32(p + 4)); }
     __device__ static double add(double a, double b) { return __dadd_rn(a, b); }
 };
+
+// One 16-B vector <-> its VEC elements.
+template <typename T>
+__device__ inline void unpack(const u32x4& r, T* o) {
+    if constexpr (sizeof(T) == 4) {
+        o[0] = Elem<T>::from_bits(r.x, 0); o[1] = Elem<T>::from_bits(r.y, 0);
+        o[2] = Elem<T>::from_bits(r.z, 0); o[3] = Elem<T>::from_bits(r.w, 0);
+    } else {
+        o[0] = Elem<T>::from_bits(r.x, r.y); o[1] = Elem<T>::from_bits(r.z, r.w);
+    }
+}
+template <typename T>
+__device__ inline u32x4 pack(const T* v) {
+    u32x4 r;
+    if constexpr (sizeof(T) == 4) {
+        r.x = __builtin_bit_cast(uint32_t, v[0]); r.y = __builtin_bit_cast(uint32_t, v[1]);
+        r.z = __builtin_bit_cast(uint32_t, v[2]); r.w = __builtin_bit_cast(uint32_t, v[3]);
+    } else {
+        uint64_t a = __builtin_bit_cast(uint64_t, v[0]), b = __builtin_bit_cast(uint64_t, v[1]);
+        r.x = (uint32_t)a; r.y = (uint32_t)(a >> 32); r.z = (uint32_t)b; r.w = (uint32_t)(b >> 32);
+    }
+    return r;
+}
+__device__ inline void st32(uint8_t* p, uint32_t v) { *(uint32_t*)p = v; }
+
+__host__ __device__ inline uint64_t splitmix64_dev(uint64_t x) {
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// A wave's LDS hand-over: what its lanes stored before is what any lane loads after.
+__device__ __forceinline__ void wave_lds_handover() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// AdaGrad's alpha of an element whose delta d ended above 1
+// (FloatMatrixStoreAdaGrad.java:268-272): one double divide and sqrt, rounded to float,
+// then the clamp. (The element step beside it, acc += g; delta += g*g with its last strict
+// rise, stays written out in k_reduce's apply, k_ada_flat's upd, k_ada_ident and the two
+// k_chain_ada_* steps: as a function, by reference or by value, inlined early or late, it
+// changed the register allocation or the operand order of every one of them.)
+__device__ __forceinline__ float ada_alpha(float d, float initial_alpha, float factor, float min_alpha) {
+    const float a = (float)((double)initial_alpha / ((double)factor * sqrt((double)d)));
+    return a < min_alpha ? min_alpha : a;
+}
+
+// maxDelta candidates: (valid, value, position), best = largest value,
+// then smallest position (the first in the reference's order). Associative, so
+// a block reduces them as a butterfly inside each wave, then across its waves
+// through LDS; the result lands in thread 0. Every thread of the block calls it.
+__device__ inline bool cand_better(bool ok, float v, uint64_t p, bool ok2, float v2, uint64_t p2) {
+    return ok && (!ok2 || v > v2 || (v == v2 && p < p2));
+}
+template <int WPB>
+__device__ inline void cand_block_best(bool& ok, float& v, uint64_t& p) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const float ov = __shfl_xor(v, m);
+        const uint32_t olo = (uint32_t)__shfl_xor((int)(uint32_t)p, m);
+        const uint32_t ohi = (uint32_t)__shfl_xor((int)(uint32_t)(p >> 32), m);
+        const bool ook = __shfl_xor((int)ok, m) != 0;
+        const uint64_t op = (uint64_t)olo | ((uint64_t)ohi << 32);
+        if (cand_better(ook, ov, op, ok, v, p)) { ok = true; v = ov; p = op; }
+    }
+    if constexpr (WPB > 1) {
+        __shared__ float sv[WPB];
+        __shared__ uint64_t sp[WPB];
+        __shared__ int sok[WPB];
+        const int w = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) { sv[w] = v; sp[w] = p; sok[w] = ok; }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 1; i < WPB; ++i)
+                if (cand_better(sok[i] != 0, sv[i], sp[i], ok, v, p)) { ok = true; v = sv[i]; p = sp[i]; }
+    }
+}
+// The best of cand[i], cand[i + step], ... below n, folded into (ok, v, p).
+__device__ inline void cand_scan(const DeltaCand* __restrict__ cand, int64_t i, int64_t n, int64_t step, bool& ok,
+                                 float& v, uint64_t& p) {
+    for (; i < n; i += step) {
+        const DeltaCand c = cand[i];
+        if (cand_better(c.valid != 0, c.value, c.pos, ok, v, p)) { ok = true; v = c.value; p = c.pos; }
+    }
+}
+// The candidate as a block's thread 0 stores it (after cand_block_best).
+__device__ __forceinline__ DeltaCand cand_of(const bool& ok, const float& v, const uint64_t& p) {
+    DeltaCand c;
+    c.value = v; c.valid = ok; c.pos = p;
+    return c;
+}
 
 }  // namespace dml

@@ -1,5 +1,6 @@
-// dml_internal.h — types shared by the HIP kernels (dml_kernels.hip) and the
-// C-ABI host implementation (dml_store.hip). Not part of the public ABI.
+// dml_internal.h — types shared by the HIP kernel files and the C-ABI host
+// implementation (dml_store*.hip, dml_prereduce.hip), and the kernels' launchers.
+// Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -203,7 +204,8 @@ struct LaunchEv {
     hipEvent_t stop = nullptr;
 };
 
-// ---- launchers (dml_kernels.hip) ----
+// ---- launchers, grouped by the file that holds the kernels ----
+// ---- dense push path (dml_kernels.hip) ----
 hipError_t launch_index(const Batch& bt, int nb, int64_t max_nrec, int64_t stride, int K,
                         int64_t first, int64_t rows, int32_t* slot, uint32_t* rowflag, Ctrl* ctrl,
                         uint64_t tail_cut, hipStream_t st);
@@ -226,20 +228,60 @@ hipError_t launch_reduce(int vtype, int mode, void* shard, int64_t rows, int32_t
 hipError_t launch_rollback_i32(int32_t* shard, int64_t rows, int32_t cols, const Batch& bt, int nb,
                                int64_t stride, int K, const int32_t* slot, const uint32_t* rowflag, Ctrl* ctrl,
                                uint64_t tail_cut, hipStream_t st, RowMap rm = {});
+// `cand` holds n candidates plus kMdParts entries of scratch after them.
+constexpr int kMdParts = 256;
+hipError_t launch_maxdelta_finalize(DeltaCand* cand, int64_t n, MaxDelta* md, const Batch& bt, int nb,
+                                    int64_t stride, int K, int V, hipStream_t st, int mode = kMdApply,
+                                    const Ctrl* ctrl = nullptr);
+
+// ---- chained reduce-scatter steps and commits (dml_chain.hip) ----
 // After the chained int32 step's rollback (one wave): a set Ctrl::neg_pos closes an open
 // record (pos, the key read from the push at pos, col, ring step); the word is reset.
 hipError_t launch_chain_i32_verdict(const Batch& bt, int nb, int64_t stride, int K, Ctrl* ctrl, ChainI32Rec* rec,
                                     int32_t step, hipStream_t st, LaunchEv ev = {});
 // The owner's commit: the home record closes the store's open record (sticky).
 hipError_t launch_chain_i32_merge(ChainI32Rec* store_rec, const ChainI32Rec* home, hipStream_t st);
-// `cand` holds n candidates plus kMdParts entries of scratch after them.
-constexpr int kMdParts = 256;
-hipError_t launch_maxdelta_finalize(DeltaCand* cand, int64_t n, MaxDelta* md, const Batch& bt, int nb,
-                                    int64_t stride, int K, int V, hipStream_t st, int mode = kMdApply,
-                                    const Ctrl* ctrl = nullptr);
+// Chained reduce-scatter step of an AdaGrad matrix (DESIGN.md §6): the planes beside
+// RowMap::base / RowMap::out (data). Marks: one uint32 per task row, non-zero = some
+// rank's accepted push listed the row in this call; base_marks == null reads as all
+// clear (ring step 0).
+struct ChainAda {
+    const float* base_delta;
+    float* out_delta;
+    const uint32_t* base_marks;
+    uint32_t* out_marks;
+    DeltaCand* cand;  // one per block (chain_ada_blocks)
+};
+// ident: k_chain_ada_ident (every push confirmed identity by k_ident_full, rows of
+// whole 16-B vectors); otherwise k_chain_ada_rows over the slot table.
+int64_t chain_ada_blocks(bool ident, int64_t ntask, int32_t cols);
+hipError_t launch_chain_ada(bool ident, int64_t ntask, int32_t cols, const Batch& bt, int nb, int64_t stride, int K,
+                            int32_t* slot, const Ctrl* ctrl, RowMap rm, const ChainAda& ca, hipStream_t st,
+                            int64_t* ncand_out, LaunchEv ev);
+// The owner's commit of the slice that came home: data, delta, alpha where marked and
+// delta > 1 (ada's parameters), and the running maxDelta = *rec.
+hipError_t launch_chain_ada_commit(float* data, float* delta, float* alpha, MaxDelta* md, const float* sdata,
+                                   const float* sdelta, const uint32_t* marks, const MaxDelta* rec, int64_t rows,
+                                   int32_t cols, const AdaArgs& ada, hipStream_t st);
+
+// ---- two-moment AdaGrad (dml_moments.hip; sharded path) ----
+// Per-rank [row][Σu | Σu²] pre-reduce pieces (flat shapes: cols % 4 == 0, rows under
+// 4 KiB), and the owner apply of the reduce-scattered moments (+ maxDelta finalize;
+// ada.cand holds kMomentBlocks entries).
+constexpr int kMomentBlocks = 2048;
+hipError_t launch_moments(int64_t ntask, int32_t cols, const Batch& bt, int nb, int64_t stride, int K, int32_t* slot,
+                          const Ctrl* ctrl, RowMap rm, hipStream_t st, LaunchEv ev);
+hipError_t launch_ada_moments(float* shard, const float* src, int64_t rows, int32_t cols, const AdaArgs& ada,
+                              MaxDelta* md, int64_t first, hipStream_t st, LaunchEv ev);
+
+// ---- a store's other operations (dml_ops.hip) ----
 hipError_t launch_array_rollback_i32(int32_t* shard, int64_t rows, const uint8_t* base, int64_t nrec,
                                      int b_global, int64_t stride, int K, int64_t first, Ctrl* ctrl,
                                      uint64_t tail_cut, hipStream_t st);
+hipError_t launch_key_rows(const uint8_t* base, int64_t nrec, int64_t stride, int K, int64_t first, int64_t rows,
+                           int32_t* out, hipStream_t st);
+hipError_t launch_rand(int vtype, void* p, int64_t rows, int32_t cols, uint64_t s0, hipStream_t st);
+hipError_t launch_bswap(int V, const void* src, void* dst, int64_t n, hipStream_t st);
 hipError_t launch_fill(int vtype, void* p, int64_t n, double v, hipStream_t st);
 hipError_t launch_fill_f32(float* p, int64_t n, float v, hipStream_t st);
 hipError_t launch_apply_dense(int vtype, void* shard, const void* src, int64_t n, hipStream_t st);
@@ -252,7 +294,9 @@ hipError_t launch_fetch(int vtype, const void* shard, const float* alpha, int32_
 hipError_t launch_fetch_checked(int vtype, const void* shard, const float* alpha, int32_t cols, const int64_t* keys,
                                 int64_t n, int64_t first, int64_t last, uint8_t* out, int64_t rec, int K,
                                 int value_slot, unsigned long long* bad, hipStream_t st);
-// k_fetch_vec (dml_fetch.hip): the same records as one stream of whole 16-byte stores.
+
+// ---- vectorised fetch (dml_fetch.hip) ----
+// k_fetch_vec: the same records as one stream of whole 16-byte stores.
 // `variant` (diagnostic, bits kFetchVar*) picks the launch shapes DESIGN.md §4.10 compares.
 constexpr int kFetchVarLoadMask = 3;  // 0: by record length, 1: every dword singly, 2: 16-byte shard loads
 constexpr int kFetchVarGather = 1, kFetchVarVload = 2;
@@ -269,7 +313,18 @@ hipError_t launch_fetch_vec(int vtype, const void* shard, const float* alpha, in
                             int value_slot, unsigned long long* bad, int variant, hipStream_t st);
 // Behind a list fetch: *bad (this fetch's lowest bad index) into the sticky verdict, *bad reset.
 hipError_t launch_fetch_verdict(unsigned long long* bad, const int64_t* keys, FetchVerdict* v, hipStream_t st);
-hipError_t launch_bswap(int V, const void* src, void* dst, int64_t n, hipStream_t st);
+
+// ---- diagnostics: synthetic data, streaming ceilings, floors (dml_diag.hip) ----
+hipError_t launch_synth_fill(int vtype, void* p, int64_t n, uint64_t s0, hipStream_t st);
+hipError_t launch_stream(bool copy, void* dst, const void* src, int64_t n16, hipStream_t st, LaunchEv ev);
+hipError_t launch_rmw_floor(float* a, const uint32_t* idx, const float* v, int64_t n, hipStream_t st, LaunchEv ev);
+hipError_t launch_dense_floor(const float* data, float* out, float* delta, const Batch& bt, int nb, int64_t stride,
+                              int K, int32_t cols, int64_t elems, hipStream_t st, LaunchEv ev);
+hipError_t launch_gather_floor(int32_t* shard, int32_t cols, const int32_t* trow, const int32_t* tptr,
+                               const uint64_t* addr, int64_t ntouched, hipStream_t st, LaunchEv ev);
+// One rank's ring reduce-scatter footprint: one kernel of `channels` blocks.
+hipError_t launch_ring_rs(int vtype, const void* part, void* recv, void* land, int64_t chunk_bytes, int world,
+                          int rank, int channels, hipStream_t st);
 hipError_t launch_synth_dense(uint8_t* out, int K, int vtype, int64_t first, int64_t shard_rows, int64_t nrec,
                               int32_t cols, uint64_t s0, uint64_t pa, uint64_t pc, hipStream_t st);
 hipError_t launch_synth_sparse(uint8_t* out, int K, int vtype, int value_stride, int64_t first,
@@ -359,51 +414,7 @@ hipError_t sparse_replay(int vtype, void* shard, const SpPlan& pl, const SpLayou
                          int64_t stride, int K, int64_t first, int64_t rows, Ctrl* ctrl, uint64_t tail_cut,
                          hipStream_t st);
 
-// Two-moment AdaGrad (sharded path): per-rank [row][Σu | Σu²]
-// pre-reduce pieces (flat shapes: cols % 4 == 0, rows under 4 KiB), and the owner
-// apply of the reduce-scattered moments (+ maxDelta finalize; ada.cand holds
-// kMomentBlocks entries).
-constexpr int kMomentBlocks = 2048;
-hipError_t launch_moments(int64_t ntask, int32_t cols, const Batch& bt, int nb, int64_t stride, int K, int32_t* slot,
-                          const Ctrl* ctrl, RowMap rm, hipStream_t st, LaunchEv ev);
-hipError_t launch_ada_moments(float* shard, const float* src, int64_t rows, int32_t cols, const AdaArgs& ada,
-                              MaxDelta* md, int64_t first, hipStream_t st, LaunchEv ev);
-
-// Chained reduce-scatter step of an AdaGrad matrix (DESIGN.md §6): the planes beside
-// RowMap::base / RowMap::out (data). Marks: one uint32 per task row, non-zero = some
-// rank's accepted push listed the row in this call; base_marks == null reads as all
-// clear (ring step 0).
-struct ChainAda {
-    const float* base_delta;
-    float* out_delta;
-    const uint32_t* base_marks;
-    uint32_t* out_marks;
-    DeltaCand* cand;  // one per block (chain_ada_blocks)
-};
-// ident: k_chain_ada_ident (every push confirmed identity by k_ident_full, rows of
-// whole 16-B vectors); otherwise k_chain_ada_rows over the slot table.
-int64_t chain_ada_blocks(bool ident, int64_t ntask, int32_t cols);
-hipError_t launch_chain_ada(bool ident, int64_t ntask, int32_t cols, const Batch& bt, int nb, int64_t stride, int K,
-                            int32_t* slot, const Ctrl* ctrl, RowMap rm, const ChainAda& ca, hipStream_t st,
-                            int64_t* ncand_out, LaunchEv ev);
-// The owner's commit of the slice that came home: data, delta, alpha where marked and
-// delta > 1 (ada's parameters), and the running maxDelta = *rec.
-hipError_t launch_chain_ada_commit(float* data, float* delta, float* alpha, MaxDelta* md, const float* sdata,
-                                   const float* sdelta, const uint32_t* marks, const MaxDelta* rec, int64_t rows,
-                                   int32_t cols, const AdaArgs& ada, hipStream_t st);
-
-hipError_t launch_stream(bool copy, void* dst, const void* src, int64_t n16, hipStream_t st, LaunchEv ev);
-hipError_t launch_rmw_floor(float* a, const uint32_t* idx, const float* v, int64_t n, hipStream_t st, LaunchEv ev);
-hipError_t launch_dense_floor(const float* data, float* out, float* delta, const Batch& bt, int nb, int64_t stride,
-                              int K, int32_t cols, int64_t elems, hipStream_t st, LaunchEv ev);
-hipError_t launch_gather_floor(int32_t* shard, int32_t cols, const int32_t* trow, const int32_t* tptr,
-                               const uint64_t* addr, int64_t ntouched, hipStream_t st, LaunchEv ev);
-hipError_t launch_rand(int vtype, void* p, int64_t rows, int32_t cols, uint64_t s0, hipStream_t st);
-hipError_t launch_synth_fill(int vtype, void* p, int64_t n, uint64_t s0, hipStream_t st);
-hipError_t launch_key_rows(const uint8_t* base, int64_t nrec, int64_t stride, int K, int64_t first, int64_t rows,
-                           int32_t* out, hipStream_t st);
-
-// ---- launch shape of a dense reduce ----
+// ---- launch shape of a dense reduce (dml_kernels.hip) ----
 // Vector geometry of a value type: elements per 16-B vector, bytes per element.
 struct VecGeom {
     int vec, elem;
@@ -463,9 +474,6 @@ hipError_t launch_flat_ident(int vtype, int mode, void* shard, int64_t rows, int
 // Ctrl after the index (hctrl) and the pushes' record counts (`need` per push: the
 // model rows).
 bool flat_ident_ok(const Ctrl& hctrl, const Batch& bt, int nb, int64_t need, uint64_t tail_cut);
-// One rank's ring reduce-scatter footprint (diagnostic): one kernel of `channels` blocks.
-hipError_t launch_ring_rs(int vtype, const void* part, void* recv, void* land, int64_t chunk_bytes, int world,
-                          int rank, int channels, hipStream_t st);
 // Task rows per wave of k_flat_ident at this width (a row map's blocks must hold whole waves).
 int flat_ident_rows_per_wave(int vtype, int32_t cols);
 // row shapes whose reduce runs identity-speculative chunks (k_reduce_rows FULL, k_reduce_flat)

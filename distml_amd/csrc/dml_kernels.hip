@@ -1,4 +1,8 @@
-// dml_kernels.hip — CDNA4 (gfx950) kernels of the parameter-server push path.
+// dml_kernels.hip — CDNA4 (gfx950) kernels of a store's dense push path: the key index,
+// the ordered reduces and the maxDelta finalize, with the table that picks a reduce's
+// launch shape. Driven by dml_store.hip and dml_prereduce.hip. The chained steps beside
+// them are dml_chain.hip, the two-moment AdaGrad path dml_moments.hip, a store's other
+// kernels dml_ops.hip, the diagnostic ones dml_diag.hip.
 //
 // Compiled with -ffp-contract=off and IEEE denormals (Java forbids FMA
 // contraction and flush-to-zero, JLS 15.4 / 4.2.3): every `acc + v` below is
@@ -23,24 +27,10 @@
 //                   chunk for the flat family)
 //   k_ident_check, k_ident_full, k_assign_cols  the index-chain kernels of identity
 //                   speculation and slot reuse (which pushes need no key index)
-//   k_moments_flat, k_ada_moments  the sharded two-moment AdaGrad pieces and apply
-//   k_array_rollback int32 array stores: undo every add after the first negative
-//                   counter (IntArrayStore.java:97-113); the arrays' ordered
-//                   scatter-add itself is the partition + leaf path of dml_sparse.hip
-//   k_chain_ada_ident, k_chain_ada_rows, k_chain_ada_commit  the chained
-//                   reduce-scatter's step and owner commit for AdaGrad matrices
-//                   (data + delta planes, touched marks, maxDelta candidates; one
-//                   documented divergence, the alpha of an element whose delta comes
-//                   home NaN — dml_group_push_exchange is the path without it)
-//   k_chain_i32_verdict, k_chain_i32_merge  the chained reduce-scatter of int32
-//                   matrices: kChainCheckI32 (k_reduce_rows / k_reduce) sums a step
-//                   with the check after every add, k_reduce<kRollbackI32> undoes the
-//                   adds past the first negative, the verdict closes the slice's record
-//   k_fetch, k_bswap, k_fill, k_apply_dense, k_synth_*  — fetch / checkpoint /
-//                   init / owner-apply / synthetic data.
+//   k_maxdelta_part, k_maxdelta  AdaGrad's maxDelta / row / col from the reduces'
+//                   per-block candidates (FloatMatrixStoreAdaGrad.java:273-277)
 #include "dml_device.h"
-
-#include <hip/hip_ext.h>
+#include "dml_launch.h"
 
 #include <algorithm>
 #include <climits>
@@ -56,36 +46,8 @@ constexpr int kC5Wpb = 2, kC5Rpw = 4;  // k_reduce_rows DEPTH 3 (config 5): wave
 constexpr int kD3Waves = 1;            // DEPTH 3: minimum waves per SIMD its registers must allow
 constexpr int kAdaFlatWaves = 4;       // k_ada_flat: waves per block
 
-__host__ __device__ inline uint64_t splitmix64_dev(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 uint64_t splitmix64(uint64_t x) { return splitmix64_dev(x); }
 thread_local const char* g_kernel_name = nullptr;
-
-template <typename T>
-__device__ inline void unpack(const u32x4& r, T* o) {
-    if constexpr (sizeof(T) == 4) {
-        o[0] = Elem<T>::from_bits(r.x, 0); o[1] = Elem<T>::from_bits(r.y, 0);
-        o[2] = Elem<T>::from_bits(r.z, 0); o[3] = Elem<T>::from_bits(r.w, 0);
-    } else {
-        o[0] = Elem<T>::from_bits(r.x, r.y); o[1] = Elem<T>::from_bits(r.z, r.w);
-    }
-}
-template <typename T>
-__device__ inline u32x4 pack(const T* v) {
-    u32x4 r;
-    if constexpr (sizeof(T) == 4) {
-        r.x = __builtin_bit_cast(uint32_t, v[0]); r.y = __builtin_bit_cast(uint32_t, v[1]);
-        r.z = __builtin_bit_cast(uint32_t, v[2]); r.w = __builtin_bit_cast(uint32_t, v[3]);
-    } else {
-        uint64_t a = __builtin_bit_cast(uint64_t, v[0]), b = __builtin_bit_cast(uint64_t, v[1]);
-        r.x = (uint32_t)a; r.y = (uint32_t)(a >> 32); r.z = (uint32_t)b; r.w = (uint32_t)(b >> 32);
-    }
-    return r;
-}
 
 // ---------------------------------------------------------------------------
 // k_index: one thread per record of push b (blockIdx.y): slot[row][b] = record.
@@ -247,38 +209,6 @@ hipError_t launch_index(const Batch& bt, int nb, int64_t max_nrec, int64_t strid
     hipLaunchKernelGGL(k_index, dim3(grid), dim3(256), 0, st, bt, nb, nchunk, stride, K, first, rows, slot, rowflag,
                        ctrl, tail_cut);
     return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// AdaGrad maxDelta candidates: (valid, value, position), best = largest value,
-// then smallest position (the first in the reference's order). Associative, so
-// a block reduces them as a butterfly inside each wave, then across its waves
-// through LDS; the result lands in thread 0. Every thread of the block calls it.
-__device__ inline bool cand_better(bool ok, float v, uint64_t p, bool ok2, float v2, uint64_t p2) {
-    return ok && (!ok2 || v > v2 || (v == v2 && p < p2));
-}
-template <int WPB>
-__device__ inline void cand_block_best(bool& ok, float& v, uint64_t& p) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        const float ov = __shfl_xor(v, m);
-        const uint32_t olo = (uint32_t)__shfl_xor((int)(uint32_t)p, m);
-        const uint32_t ohi = (uint32_t)__shfl_xor((int)(uint32_t)(p >> 32), m);
-        const bool ook = __shfl_xor((int)ok, m) != 0;
-        const uint64_t op = (uint64_t)olo | ((uint64_t)ohi << 32);
-        if (cand_better(ook, ov, op, ok, v, p)) { ok = true; v = ov; p = op; }
-    }
-    if constexpr (WPB > 1) {
-        __shared__ float sv[WPB];
-        __shared__ uint64_t sp[WPB];
-        __shared__ int sok[WPB];
-        const int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { sv[w] = v; sp[w] = p; sok[w] = ok; }
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (int i = 1; i < WPB; ++i)
-                if (cand_better(sok[i] != 0, sv[i], sp[i], ok, v, p)) { ok = true; v = sv[i]; p = sp[i]; }
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -573,6 +503,7 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
                     for (int e = 0; e < VEC; ++e) {
                         na[e] = 0.f;
                         if (e < nv[c] && lg[c][e] > 1.0f) {
+                            // ada_alpha(), restated: the call changes this kernel's code
                             na[e] = (float)((double)ada.initial_alpha / ((double)ada.factor * sqrt((double)lg[c][e])));
                             if (na[e] < ada.min_alpha) na[e] = ada.min_alpha;
                         } else {
@@ -608,11 +539,7 @@ __global__ __launch_bounds__(64 * WPB) void k_reduce(T* __restrict__ shard, int6
 
     if constexpr (MODE == kAdaGrad) {
         cand_block_best<WPB>(cand_ok, cand_v, cand_p);
-        if (threadIdx.x == 0) {
-            DeltaCand c;
-            c.value = cand_v; c.valid = cand_ok; c.pos = cand_p;
-            ada.cand[blockIdx.x] = c;
-        }
+        if (threadIdx.x == 0) ada.cand[blockIdx.x] = cand_of(cand_ok, cand_v, cand_p);
     }
 }
 
@@ -1167,9 +1094,7 @@ __global__ __launch_bounds__(256) void k_reduce_flat(T* __restrict__ shard, int6
         }
         ls[rl * kMaxW + b] = v;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handover();
 
     // this lane's vectors: (row << 16 | vector within the row); bit j of `on` / `wr`:
     // the vector belongs to a row this batch updates / is written back
@@ -1470,9 +1395,7 @@ __global__ __launch_bounds__(NW * 64) void k_ada_flat(float* __restrict__ shard,
                 }
                 ls[rl * kMaxW + b] = v;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_handover();
         }
         const int nvec = nrow * NV;
 #pragma unroll
@@ -1582,6 +1505,7 @@ __global__ __launch_bounds__(NW * 64) void k_ada_flat(float* __restrict__ shard,
             for (int e = 0; e < VEC; ++e) {
                 na[e] = 0.f;
                 if (lg[j][e] > 1.0f) {
+                    // ada_alpha(), restated: the call changes this kernel's code
                     na[e] = (float)((double)ada.initial_alpha / ((double)ada.factor * sqrt((double)lg[j][e])));
                     if (na[e] < ada.min_alpha) na[e] = ada.min_alpha;
                 } else {
@@ -1607,35 +1531,11 @@ __global__ __launch_bounds__(NW * 64) void k_ada_flat(float* __restrict__ shard,
         }
     }
     cand_block_best<NW>(cand_ok, cand_v, cand_p);
-    if (threadIdx.x == 0) {
-        DeltaCand c;
-        c.value = cand_v;
-        c.valid = cand_ok;
-        c.pos = cand_p;
-        ada.cand[blockIdx.x] = c;
-    }
+    if (threadIdx.x == 0) ada.cand[blockIdx.x] = cand_of(cand_ok, cand_v, cand_p);
 }
-
-
-// Occupancy cap: dynamic LDS (unused by the kernels) so that at most `bpc`
-// 256-thread blocks fit on a CU (160 KiB of LDS per CU). 0 = no cap.
-constexpr unsigned kLdsPerCU = 160 * 1024;
-inline unsigned lds_for_blocks_per_cu(int bpc) { return bpc > 0 ? kLdsPerCU / (unsigned)(bpc + 1) + 256u : 0u; }
 
 // Grid of the int32 rollback: 256 CUs x 8 four-wave blocks; its waves stride over the tasks.
 constexpr int64_t kRollbackBlocks = 2048;
-
-// One launch of `kernel`: its start / stop events ride in the dispatch packet when the
-// caller carries any (hipExtLaunchKernel); a plain launch otherwise.
-template <typename... KA, typename... A>
-static inline hipError_t launch_k(void (*kernel)(KA...), dim3 grid, dim3 block, unsigned lds, hipStream_t st,
-                                  LaunchEv ev, const A&... a) {
-    if (ev.start || ev.stop)
-        hipExtLaunchKernelGGL(kernel, grid, block, lds, st, ev.start, ev.stop, 0, static_cast<KA>(a)...);
-    else
-        hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<KA>(a)...);
-    return hipGetLastError();
-}
 
 // The arguments of a dense reduce launch, as launch_reduce receives them.
 struct ReduceArgs {
@@ -1756,24 +1656,19 @@ static hipError_t launch_reduce_t(const ReduceShape& s, const ReduceArgs& a) {
         constexpr ReduceShape S = kReduceShapes[ROW];
         int64_t nblocks = shape_blocks(s, a.rows);
         if constexpr (MODE == kRollbackI32) nblocks = std::min<int64_t>(nblocks, kRollbackBlocks);  // its waves stride
-        if (a.nblocks_out) *a.nblocks_out = nblocks;
-        if (nblocks <= 0) return hipSuccess;
-        const dim3 grid((unsigned)nblocks), block(64 * S.wpb);
         const unsigned occ_lds = lds_for_blocks_per_cu(S.bpc);
         if constexpr (S.family == kFamRows) {
-            static const std::string kn = kname("k_reduce_rows", type_name<T>(), MODE, S.cpw, S.rpw, S.nt_loads, S.full,
-                                                S.depth, S.wpb, (int)S.store);
-            g_kernel_name = kn.c_str();
-            return launch_k(k_reduce_rows<T, MODE, S.cpw, S.rpw, S.nt_loads, S.full, S.depth, S.wpb, S.store>, grid,
-                            block, occ_lds, a.st, a.ev, (T*)a.shard, a.rows, a.cols, s.ngroups, a.bt, a.nb, a.stride,
-                            a.K, const_cast<int32_t*>(a.slot), a.rowflag, a.ctrl, a.tail_cut, a.rm);
+            return launch_named<k_reduce_rows<T, MODE, S.cpw, S.rpw, S.nt_loads, S.full, S.depth, S.wpb, S.store>>(
+                std::make_tuple("k_reduce_rows", type_name<T>(), MODE, S.cpw, S.rpw, S.nt_loads, S.full, S.depth, S.wpb,
+                                (int)S.store),
+                nblocks, a.nblocks_out, 64 * S.wpb, occ_lds, a.st, a.ev, (T*)a.shard, a.rows, a.cols, s.ngroups, a.bt,
+                a.nb, a.stride, a.K, const_cast<int32_t*>(a.slot), a.rowflag, a.ctrl, a.tail_cut, a.rm);
         } else {
             constexpr bool SNT = S.store != kStCached;
-            static const std::string kn = kname("k_reduce", type_name<T>(), MODE, S.group, S.nt_loads, S.wpb, SNT, S.cpw);
-            g_kernel_name = kn.c_str();
-            return launch_k(k_reduce<T, MODE, S.group, S.nt_loads, S.wpb, SNT, S.cpw>, grid, block, occ_lds, a.st,
-                            a.ev, (T*)a.shard, a.rows, a.cols, s.ngroups, a.bt, a.nb, a.stride, a.K, a.slot,
-                            a.rowflag, a.ctrl, a.tail_cut, a.ada, a.rm);
+            return launch_named<k_reduce<T, MODE, S.group, S.nt_loads, S.wpb, SNT, S.cpw>>(
+                std::make_tuple("k_reduce", type_name<T>(), MODE, S.group, S.nt_loads, S.wpb, SNT, S.cpw), nblocks,
+                a.nblocks_out, 64 * S.wpb, occ_lds, a.st, a.ev, (T*)a.shard, a.rows, a.cols, s.ngroups, a.bt, a.nb,
+                a.stride, a.K, a.slot, a.rowflag, a.ctrl, a.tail_cut, a.ada, a.rm);
         }
     }
 }
@@ -1813,9 +1708,6 @@ static hipError_t with_type_mode(int vtype, int mode, F f) {
     return hipErrorInvalidValue;
 }
 
-// Blocks of a flat launch: R rows per wave, nw waves per block.
-static int64_t flat_blocks(int64_t rows, int R, int nw) { return ((rows + R - 1) / R + nw - 1) / nw; }
-
 // k_reduce_flat launch (narrow dense rows, see the kernel): R rows per wave.
 // One push per round: JMAX 8 (R = 10 rows at 200 columns) measured within 2 % of
 // 4 x 1, 4 x 2, 8 x 2 and 4 x 4 (config 4, ascending and permuted), and of
@@ -1828,14 +1720,10 @@ template <typename T, int MODE>
 static hipError_t launch_flat(const ReduceArgs& a) {
     constexpr int JMAX = 12, PB = 1;
     const int R = rows_per_wave(JMAX, a.cols / Elem<T>::VEC);
-    const int64_t nblocks = flat_blocks(a.rows, R, 4);
-    if (a.nblocks_out) *a.nblocks_out = nblocks;
-    if (nblocks <= 0) return hipSuccess;
-    static const std::string kn = kname("k_reduce_flat", type_name<T>(), MODE, JMAX, PB);
-    g_kernel_name = kn.c_str();
-    return launch_k(k_reduce_flat<T, MODE, JMAX, PB>, dim3((unsigned)nblocks), dim3(256), 0, a.st, a.ev, (T*)a.shard,
-                    a.rows, a.cols, R, a.bt, a.nb, a.stride, a.K, const_cast<int32_t*>(a.slot), a.rowflag, a.ctrl,
-                    a.tail_cut, a.rm);
+    return launch_named<k_reduce_flat<T, MODE, JMAX, PB>>(
+        std::make_tuple("k_reduce_flat", type_name<T>(), MODE, JMAX, PB), flat_blocks(a.rows, R, 4), a.nblocks_out, 256,
+        0, a.st, a.ev, (T*)a.shard, a.rows, a.cols, R, a.bt, a.nb, a.stride, a.K, const_cast<int32_t*>(a.slot),
+        a.rowflag, a.ctrl, a.tail_cut, a.rm);
 }
 
 // k_flat_ident launch: the all-identity chunks of the flat shape (the host checked
@@ -1856,13 +1744,9 @@ hipError_t launch_flat_ident(int vtype, int mode, void* shard, int64_t rows, int
         using T = typename decltype(t)::type;
         constexpr int MODE = decltype(m)::value, J = kFlatIdentJ, D = 3, NW = kFlatIdentWaves;  // D: pushes in flight
         const int R = flat_ident_rows_per_wave(vtype, cols);
-        const int64_t nblocks = flat_blocks(rows, R, NW);
-        if (nblocks_out) *nblocks_out = nblocks;
-        if (nblocks <= 0) return hipSuccess;
-        static const std::string kn = kname("k_flat_ident", type_name<T>(), MODE, J, D, NW);
-        g_kernel_name = kn.c_str();
-        return launch_k(k_flat_ident<T, MODE, J, D, NW>, dim3((unsigned)nblocks), dim3(NW * 64), 0, st, ev, (T*)shard,
-                        rows, cols, R, bt, nb, stride, K, ctrl, rm);
+        return launch_named<k_flat_ident<T, MODE, J, D, NW>>(
+            std::make_tuple("k_flat_ident", type_name<T>(), MODE, J, D, NW), flat_blocks(rows, R, NW), nblocks_out,
+            NW * 64, 0, st, ev, (T*)shard, rows, cols, R, bt, nb, stride, K, ctrl, rm);
     });
 }
 
@@ -1905,14 +1789,10 @@ bool spec_shape(int vtype, int32_t cols) {
 static hipError_t launch_ada_flat(const ReduceArgs& a) {
     constexpr int JMAX = 4, PB = 2, NW = kAdaFlatWaves;
     const int R = rows_per_wave(JMAX, a.cols / 4);
-    const int64_t nblocks = flat_blocks(a.rows, R, NW);
-    if (a.nblocks_out) *a.nblocks_out = nblocks;
-    if (nblocks <= 0) return hipSuccess;
-    static const std::string kn = kname("k_ada_flat", JMAX, PB, NW);
-    g_kernel_name = kn.c_str();
-    return launch_k(k_ada_flat<JMAX, PB, NW>, dim3((unsigned)nblocks), dim3(NW * 64), 0, a.st, a.ev, (float*)a.shard,
-                    a.rows, a.cols, R, a.bt, a.nb, a.stride, a.K, const_cast<int32_t*>(a.slot), a.rowflag, a.ctrl,
-                    a.tail_cut, a.ada);
+    return launch_named<k_ada_flat<JMAX, PB, NW>>(
+        std::make_tuple("k_ada_flat", JMAX, PB, NW), flat_blocks(a.rows, R, NW), a.nblocks_out, NW * 64, 0, a.st, a.ev,
+        (float*)a.shard, a.rows, a.cols, R, a.bt, a.nb, a.stride, a.K, const_cast<int32_t*>(a.slot), a.rowflag, a.ctrl,
+        a.tail_cut, a.ada);
 }
 
 // k_ada_ident: k_ada_flat for the AdaGrad chunks the host has seen to be all identity
@@ -2001,8 +1881,7 @@ __global__ __launch_bounds__(256) void k_ada_ident(float* __restrict__ shard, in
         for (int e = 0; e < VEC; ++e) {
             na[e] = 0.f;
             if (lg[u][e] > 1.0f) {
-                na[e] = (float)((double)ada.initial_alpha / ((double)ada.factor * sqrt((double)lg[u][e])));
-                if (na[e] < ada.min_alpha) na[e] = ada.min_alpha;
+                na[e] = ada_alpha(lg[u][e], ada.initial_alpha, ada.factor, ada.min_alpha);
                 any_a = true;
             } else {
                 all_a = false;
@@ -2038,13 +1917,7 @@ __global__ __launch_bounds__(256) void k_ada_ident(float* __restrict__ shard, in
         cand_p = pos_of(gb, (uint64_t)(ro + e * 4));
     }
     cand_block_best<4>(cand_ok, cand_v, cand_p);
-    if (threadIdx.x == 0) {
-        DeltaCand c;
-        c.value = cand_v;
-        c.valid = cand_ok;
-        c.pos = cand_p;
-        ada.cand[blockIdx.x] = c;
-    }
+    if (threadIdx.x == 0) ada.cand[blockIdx.x] = cand_of(cand_ok, cand_v, cand_p);
 }
 
 // Blocks of a k_ada_ident launch (one maxDelta candidate each): 256·U vectors per block.
@@ -2059,14 +1932,10 @@ hipError_t launch_ada_ident(void* shard, int64_t rows, int32_t cols, const Batch
     if (nb <= 0 || nb > 4 || !vec_geom(kF32).flat_row(cols)) return hipErrorInvalidValue;
     constexpr int U = kAdaIdentU;
     const int64_t nvec = rows * cols / 4, nblocks = ada_ident_blocks(rows, cols);
-    if (ncand_out) *ncand_out = nblocks;
-    if (nblocks <= 0) return hipSuccess;
     auto launch = [&](auto n) {
         constexpr int NB = decltype(n)::value;
-        static const std::string kn = kname("k_ada_ident", U, NB);
-        g_kernel_name = kn.c_str();
-        return launch_k(k_ada_ident<U, NB>, dim3((unsigned)nblocks), dim3(256), 0, st, ev, (float*)shard, nvec, cols,
-                        bt, stride, K, ada);
+        return launch_named<k_ada_ident<U, NB>>(std::make_tuple("k_ada_ident", U, NB), nblocks, ncand_out, 256, 0, st, ev,
+                                                (float*)shard, nvec, cols, bt, stride, K, ada);
     };
     switch (nb) {
         case 1: return launch(std::integral_constant<int, 1>{});
@@ -2121,75 +1990,18 @@ hipError_t launch_rollback_i32(int32_t* shard, int64_t rows, int32_t cols, const
 }
 
 // ---------------------------------------------------------------------------
-// Chained int32 step, after the slice's rollback: one wave, lane 0. Ctrl::neg_pos holds
-// the earliest position at which one of this rank's adds left a counter of the slice
-// negative (kChainCheckI32's atomicMin over every piece of the step), or kNoPos. A set
-// word closes an open record: the position, the key of the record of the push that
-// holds it, the column, the ring step (IllegalStateException(key, col),
-// IntMatrixStore.java:174-176). The word is handed back as kNoPos for the next step.
-__global__ __launch_bounds__(64) void k_chain_i32_verdict(const Batch bt, int nb, int64_t stride, int K,
-                                                          Ctrl* __restrict__ ctrl, ChainI32Rec* __restrict__ rec,
-                                                          int32_t step) {
-    if (threadIdx.x != 0) return;
-    const unsigned long long pos = ctrl->neg_pos;
-    if (pos == kNoPos) return;
-    ctrl->neg_pos = kNoPos;
-    if (rec->pos != kNoPos) return;
-    const int gb = (int)(pos >> 40);
-    const uint64_t off = pos & kOffMask;
-    int b = 0;
-    for (int j = 0; j < nb; ++j) b = bt.bidx[j] == gb ? j : b;
-    const int64_t r = (int64_t)(off / (uint64_t)stride);
-    rec->key = ld_key(bt.base[b] + r * stride, K);
-    rec->col = (int32_t)(((int64_t)off - r * stride - (int64_t)K) / 4);
-    rec->step = step;
-    rec->pad = 0ull;
-    rec->pos = pos;
-}
-
-hipError_t launch_chain_i32_verdict(const Batch& bt, int nb, int64_t stride, int K, Ctrl* ctrl, ChainI32Rec* rec,
-                                    int32_t step, hipStream_t st, LaunchEv ev) {
-    return launch_k(k_chain_i32_verdict, dim3(1), dim3(64), 0, st, ev, bt, nb, stride, K, ctrl, rec, step);
-}
-
-// The owner's commit of a chained int32 slice: a closed home record closes the store's
-// record, once (the first verdict stays: the store is in its error state from then on).
-__global__ __launch_bounds__(64) void k_chain_i32_merge(ChainI32Rec* __restrict__ store_rec,
-                                                        const ChainI32Rec* __restrict__ home) {
-    if (threadIdx.x != 0) return;
-    if (store_rec->pos == kNoPos && home->pos != kNoPos) *store_rec = *home;
-}
-
-hipError_t launch_chain_i32_merge(ChainI32Rec* store_rec, const ChainI32Rec* home, hipStream_t st) {
-    hipLaunchKernelGGL(k_chain_i32_merge, dim3(1), dim3(64), 0, st, store_rec, home);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
 // maxDelta finalize: reduce the per-block candidates in two launches (kMdParts
 // blocks over strided slices -> cand[n .. n + kMdParts), then one block) and
 // apply the reference's strict `deltas[i] > maxDelta` update
 // (FloatMatrixStoreAdaGrad.java:273-277). One block over 10^5+ candidates was
 // bound by a single CU's load rate.
-__device__ inline void cand_scan(const DeltaCand* __restrict__ cand, int64_t i, int64_t n, int64_t step, bool& ok,
-                                 float& v, uint64_t& p) {
-    for (; i < n; i += step) {
-        const DeltaCand c = cand[i];
-        if (cand_better(c.valid != 0, c.value, c.pos, ok, v, p)) { ok = true; v = c.value; p = c.pos; }
-    }
-}
-
 __global__ __launch_bounds__(256) void k_maxdelta_part(DeltaCand* __restrict__ cand, int64_t n) {
     bool ok = false;
     float v = 0.f;
     uint64_t p = kNoPos;
     cand_scan(cand, (int64_t)blockIdx.x * 256 + threadIdx.x, n, (int64_t)gridDim.x * 256, ok, v, p);
     cand_block_best<4>(ok, v, p);
-    if (threadIdx.x == 0) {
-        DeltaCand c;
-        c.value = v; c.valid = ok; c.pos = p;
-        cand[n + blockIdx.x] = c;
-    }
+    if (threadIdx.x == 0) cand[n + blockIdx.x] = cand_of(ok, v, p);
 }
 
 __global__ __launch_bounds__(256) void k_maxdelta(const DeltaCand* __restrict__ cand, int64_t n,
@@ -2212,9 +2024,7 @@ __global__ __launch_bounds__(256) void k_maxdelta(const DeltaCand* __restrict__ 
     if (cand_better(pd.valid != 0, pd.value, pd.pos, ok, v, p)) { ok = true; v = pd.value; p = pd.pos; }
     const bool defer = mode == kMdDefer || (mode == kMdDeferIfRepeat && ctrl && ctrl->no_dup == 0u);
     if (defer) {
-        DeltaCand c;
-        c.value = v; c.valid = ok; c.pos = p;
-        md->pend = c;
+        md->pend = cand_of(ok, v, p);
         return;
     }
     md->pend.valid = 0;
@@ -2239,1039 +2049,6 @@ hipError_t launch_maxdelta_finalize(DeltaCand* cand, int64_t n, MaxDelta* md, co
     } else {
         hipLaunchKernelGGL(k_maxdelta, dim3(1), dim3(256), 0, st, cand, n, md, bt, nb, stride, K, V, mode, ctrl);
     }
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Array stores (int32): undo after the first negative counter. Records
-// [key][value] at stride K+VS; the ordered apply itself is the sorted leaf path
-// (dml_sparse.hip).
-// Undo (mod 2^32) every int32 array add positioned after the first negative.
-__global__ __launch_bounds__(256) void k_array_rollback(int32_t* __restrict__ shard, int64_t rows,
-                                                        const uint8_t* __restrict__ base, int64_t nrec, int b_global,
-                                                        int64_t stride, int K, int64_t first, Ctrl* __restrict__ ctrl,
-                                                        uint64_t tail_cut) {
-    const uint64_t neg = ctrl->neg_pos;
-    if (neg == kNoPos) return;
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= nrec) return;
-    uint64_t cut = ctrl->cutoff;
-    if (tail_cut < cut) cut = tail_cut;
-    const int64_t off = r * stride;
-    if (pos_of((uint64_t)b_global, (uint64_t)off) >= cut) return;
-    if (pos_of((uint64_t)b_global, (uint64_t)(off + K)) <= neg) return;
-    const int64_t idx = row_index(ld_key(base + off, K), first, rows);
-    if (idx < 0) return;
-    atomicSub(&shard[idx], (int32_t)ld32(base + off + K));
-}
-
-hipError_t launch_array_rollback_i32(int32_t* shard, int64_t rows, const uint8_t* base, int64_t nrec, int b_global,
-                                     int64_t stride, int K, int64_t first, Ctrl* ctrl, uint64_t tail_cut,
-                                     hipStream_t st) {
-    if (nrec <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_array_rollback, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, st, shard, rows, base,
-                       nrec, b_global, stride, K, first, ctrl, tail_cut);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-template <typename T>
-__global__ void k_fill(T* __restrict__ p, int64_t n, T v) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        p[i] = v;
-}
-static unsigned grid_for(int64_t n) {
-    int64_t g = (n + 255) / 256;
-    if (g > 8192) g = 8192;
-    return (unsigned)(g < 1 ? 1 : g);
-}
-hipError_t launch_fill(int vtype, void* p, int64_t n, double v, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    if (vtype == kF32) hipLaunchKernelGGL(k_fill<float>, dim3(grid_for(n)), dim3(256), 0, st, (float*)p, n, (float)v);
-    else if (vtype == kI32) hipLaunchKernelGGL(k_fill<int32_t>, dim3(grid_for(n)), dim3(256), 0, st, (int32_t*)p, n, (int32_t)v);
-    else hipLaunchKernelGGL(k_fill<double>, dim3(grid_for(n)), dim3(256), 0, st, (double*)p, n, v);
-    return hipGetLastError();
-}
-hipError_t launch_fill_f32(float* p, int64_t n, float v, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fill<float>, dim3(grid_for(n)), dim3(256), 0, st, p, n, v);
-    return hipGetLastError();
-}
-
-// shard += src, element-wise (owner apply after a reduce-scatter).
-template <typename T>
-__global__ __launch_bounds__(256) void k_apply_dense(T* __restrict__ shard, const T* __restrict__ src, int64_t n) {
-    constexpr int VEC = Elem<T>::VEC;
-    const int64_t nvec = n / VEC;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
-        T a[VEC], b[VEC];
-        unpack<T>(((const u32x4*)shard)[i], a);
-        unpack<T>(((const u32x4*)src)[i], b);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) a[e] = Elem<T>::add(a[e], b[e]);
-        ((u32x4*)shard)[i] = pack<T>(a);
-    }
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n - nvec * VEC) shard[nvec * VEC + t] = Elem<T>::add(shard[nvec * VEC + t], src[nvec * VEC + t]);
-}
-// int32 owner apply with IntMatrixStore's negativity check on the final counters
-// (IntMatrixStore.java:174-176): the first negative element (row-major) of the
-// first failing apply is kept in *neg (sticky: kNoPos until then); once it is
-// set, later applies are no-ops (the reference store stops at its exception).
-__global__ __launch_bounds__(256) void k_apply_dense_i32chk(int32_t* __restrict__ shard, const int32_t* __restrict__ src,
-                                                            int64_t n, unsigned long long* neg) {
-    if (__atomic_load_n(neg, __ATOMIC_RELAXED) != kNoPos) return;
-    const int64_t nvec = n / 4;
-    unsigned long long first = kNoPos;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
-        int32_t a[4], b[4];
-        unpack<int32_t>(((const u32x4*)shard)[i], a);
-        unpack<int32_t>(((const u32x4*)src)[i], b);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            a[e] = Elem<int32_t>::add(a[e], b[e]);
-            if (a[e] < 0 && first == kNoPos) first = (unsigned long long)(4 * i + e);
-        }
-        ((u32x4*)shard)[i] = pack<int32_t>(a);
-    }
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n - nvec * 4) {
-        const int64_t j = nvec * 4 + t;
-        const int32_t v = Elem<int32_t>::add(shard[j], src[j]);
-        shard[j] = v;
-        if (v < 0 && first == kNoPos) first = (unsigned long long)j;
-    }
-    if (first != kNoPos) atomicMin(neg, first);
-}
-
-// The owner apply runs beside the next call's pre-reduce: a grid
-// that fills every free wave slot keeps the pre-reduce's next blocks from being
-// placed (its waves need most of a SIMD's VGPRs). kApplyBlocks bounds it to two
-// blocks per CU; it still moves a config-2 shard's 192 MB well inside one call.
-constexpr unsigned kApplyBlocks = 512;
-
-hipError_t launch_apply_dense_i32chk(int32_t* shard, const int32_t* src, int64_t n, unsigned long long* neg,
-                                     hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_apply_dense_i32chk, dim3(kApplyBlocks), dim3(256), 0, st, shard, src, n, neg);
-    return hipGetLastError();
-}
-
-hipError_t launch_apply_dense(int vtype, void* shard, const void* src, int64_t n, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    const unsigned g = kApplyBlocks;
-    if (vtype == kF32) hipLaunchKernelGGL(k_apply_dense<float>, dim3(g), dim3(256), 0, st, (float*)shard, (const float*)src, n);
-    else if (vtype == kI32) hipLaunchKernelGGL(k_apply_dense<int32_t>, dim3(g), dim3(256), 0, st, (int32_t*)shard, (const int32_t*)src, n);
-    else hipLaunchKernelGGL(k_apply_dense<double>, dim3(g), dim3(256), 0, st, (double*)shard, (const double*)src, n);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// handleFetch encode, dense-column layouts (FloatMatrixStore.java:140-153 etc.).
-// One thread per (key, column). `value_slot` = bytes per column in the output
-// record (4/8; 8 for AdaGrad value+alpha and FloatArrayStore's 8-byte slot).
-__device__ inline void st32(uint8_t* p, uint32_t v) { *(uint32_t*)p = v; }
-
-// CHECK (dml_store_fetch_device's list form, whose keys no host loop has seen): a key outside
-// [first, last] reads nothing and writes nothing; the lowest list index of one lands in *bad.
-template <typename T, bool CHECK = false>
-__global__ void k_fetch(const T* __restrict__ shard, const float* __restrict__ alpha, int32_t cols,
-                        const int64_t* __restrict__ keys, int64_t key_lo, int64_t n, int64_t first,
-                        uint8_t* __restrict__ out, int64_t rec, int K, int value_slot, int64_t last = 0,
-                        unsigned long long* __restrict__ bad = nullptr) {
-    const int64_t total = n * (int64_t)cols;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t j = t / cols;
-        const int32_t c = (int32_t)(t - j * cols);
-        const int64_t key = keys ? keys[j] : key_lo + j;
-        const int64_t idx = key - first;
-        if constexpr (CHECK) {
-            if (key < first || key > last) {
-                if (c == 0) atomicMin(bad, (unsigned long long)j);
-                continue;
-            }
-        }
-        uint8_t* o = out + j * rec;
-        if (c == 0) {
-            st32(o, (uint32_t)key);
-            if (K == 8) st32(o + 4, (uint32_t)((uint64_t)key >> 32));
-        }
-        uint8_t* v = o + K + (int64_t)c * value_slot;
-        const T x = shard[idx * cols + c];
-        if constexpr (sizeof(T) == 4) {
-            st32(v, __builtin_bit_cast(uint32_t, x));
-        } else {
-            const uint64_t u = __builtin_bit_cast(uint64_t, x);
-            st32(v, (uint32_t)u); st32(v + 4, (uint32_t)(u >> 32));
-        }
-        if (alpha) st32(v + 4, __float_as_uint(alpha[idx * cols + c]));
-        else if (sizeof(T) == 4 && value_slot == 8) st32(v + 4, 0u);  // FloatArrayStore's zero pad
-    }
-}
-hipError_t launch_fetch(int vtype, const void* shard, const float* alpha, int32_t cols, const int64_t* keys,
-                        int64_t key_lo, int64_t n, int64_t first, uint8_t* out, int64_t rec, int K, int value_slot,
-                        hipStream_t st) {
-    const int64_t total = n * (int64_t)cols;
-    if (total <= 0) return hipSuccess;
-    const dim3 g(grid_for(total));
-    if (vtype == kF32) hipLaunchKernelGGL(k_fetch<float>, g, dim3(256), 0, st, (const float*)shard, alpha, cols, keys, key_lo, n, first, out, rec, K, value_slot);
-    else if (vtype == kI32) hipLaunchKernelGGL(k_fetch<int32_t>, g, dim3(256), 0, st, (const int32_t*)shard, alpha, cols, keys, key_lo, n, first, out, rec, K, value_slot);
-    else hipLaunchKernelGGL(k_fetch<double>, g, dim3(256), 0, st, (const double*)shard, alpha, cols, keys, key_lo, n, first, out, rec, K, value_slot);
-    return hipGetLastError();
-}
-hipError_t launch_fetch_checked(int vtype, const void* shard, const float* alpha, int32_t cols, const int64_t* keys,
-                                int64_t n, int64_t first, int64_t last, uint8_t* out, int64_t rec, int K,
-                                int value_slot, unsigned long long* bad, hipStream_t st) {
-    const int64_t total = n * (int64_t)cols;
-    if (total <= 0) return hipSuccess;
-    const dim3 g(grid_for(total));
-    if (vtype == kF32) hipLaunchKernelGGL((k_fetch<float, true>), g, dim3(256), 0, st, (const float*)shard, alpha, cols, keys, (int64_t)0, n, first, out, rec, K, value_slot, last, bad);
-    else if (vtype == kI32) hipLaunchKernelGGL((k_fetch<int32_t, true>), g, dim3(256), 0, st, (const int32_t*)shard, alpha, cols, keys, (int64_t)0, n, first, out, rec, K, value_slot, last, bad);
-    else hipLaunchKernelGGL((k_fetch<double, true>), g, dim3(256), 0, st, (const double*)shard, alpha, cols, keys, (int64_t)0, n, first, out, rec, K, value_slot, last, bad);
-    return hipGetLastError();
-}
-
-// Big-endian <-> native byte swap (DataOutputStream.writeFloat/writeInt/writeDouble).
-__global__ void k_bswap4(const uint32_t* __restrict__ s, uint32_t* __restrict__ d, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        d[i] = __builtin_bswap32(s[i]);
-}
-__global__ void k_bswap8(const uint64_t* __restrict__ s, uint64_t* __restrict__ d, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        d[i] = __builtin_bswap64(s[i]);
-}
-hipError_t launch_bswap(int V, const void* src, void* dst, int64_t n, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    if (V == 4) hipLaunchKernelGGL(k_bswap4, dim3(grid_for(n)), dim3(256), 0, st, (const uint32_t*)src, (uint32_t*)dst, n);
-    else hipLaunchKernelGGL(k_bswap8, dim3(grid_for(n)), dim3(256), 0, st, (const uint64_t*)src, (uint64_t*)dst, n);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Synthetic data (DESIGN.md §Synthetic data; CPU twin: oracle/dml_oracle.c).
-__device__ inline int32_t synth_grad_int(uint64_t h) {
-    const int32_t s = (int32_t)(h & 0xFFFF) + (int32_t)((h >> 16) & 0xFFFF) + (int32_t)((h >> 32) & 0xFFFF) +
-                      (int32_t)((h >> 48) & 0xFFFF);
-    return s - 131070;
-}
-__device__ inline void put_value(uint8_t* p, int vtype, uint64_t h) {
-    if (vtype == kF32) {
-        st32(p, __float_as_uint((float)synth_grad_int(h) * 0x1p-25f));
-    } else if (vtype == kF64) {
-        const uint64_t u = __builtin_bit_cast(uint64_t, (double)synth_grad_int(h) * 0x1p-25);
-        st32(p, (uint32_t)u); st32(p + 4, (uint32_t)(u >> 32));
-    } else {
-        st32(p, (uint32_t)((int32_t)(h % 5) - 2));
-    }
-}
-__device__ inline void put_key(uint8_t* p, int K, int64_t key) {
-    st32(p, (uint32_t)key);
-    if (K == 8) st32(p + 4, (uint32_t)((uint64_t)key >> 32));
-}
-
-// perm: record r -> row (pa*r + pc) mod n; host guarantees pa < 2^32, r < 2^32.
-__global__ void k_synth_dense(uint8_t* __restrict__ out, int K, int vtype, int64_t first, int64_t shard_rows,
-                              int64_t nrec, int32_t cols, uint64_t s0, uint64_t pa, uint64_t pc) {
-    const int V = vtype == kF64 ? 8 : 4;
-    const int64_t stride = K + (int64_t)V * cols;
-    const int64_t total = nrec * (int64_t)cols;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t r = t / cols;
-        const int32_t c = (int32_t)(t - r * cols);
-        const uint64_t row = ((pa * (uint64_t)r) % (uint64_t)shard_rows + pc) % (uint64_t)shard_rows;
-        uint8_t* rec = out + r * stride;
-        if (c == 0) put_key(rec, K, first + (int64_t)row);
-        put_value(rec + K + (int64_t)V * c, vtype, splitmix64_dev(s0 + row * (uint64_t)cols + (uint64_t)c));
-    }
-}
-hipError_t launch_synth_dense(uint8_t* out, int K, int vtype, int64_t first, int64_t shard_rows, int64_t nrec,
-                              int32_t cols, uint64_t s0, uint64_t pa, uint64_t pc, hipStream_t st) {
-    hipLaunchKernelGGL(k_synth_dense, dim3(8192), dim3(256), 0, st, out, K, vtype, first, shard_rows, nrec, cols, s0, pa, pc);
-    return hipGetLastError();
-}
-
-__global__ void k_synth_sparse(uint8_t* __restrict__ out, int K, int vtype, int value_stride, int64_t first,
-                               int64_t key_space, int64_t nrec, uint64_t s0, uint64_t pa, uint64_t pc) {
-    const int64_t stride = K + value_stride;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrec; r += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t i = ((pa * (uint64_t)r) % (uint64_t)key_space + pc) % (uint64_t)key_space;
-        uint8_t* rec = out + r * stride;
-        put_key(rec, K, first + (int64_t)i);
-        for (int z = 0; z < value_stride; z += 4) st32(rec + K + z, 0u);
-        put_value(rec + K, vtype, splitmix64_dev(s0 + i));
-    }
-}
-hipError_t launch_synth_sparse(uint8_t* out, int K, int vtype, int value_stride, int64_t first, int64_t key_space,
-                               int64_t nrec, uint64_t s0, uint64_t pa, uint64_t pc, hipStream_t st) {
-    hipLaunchKernelGGL(k_synth_sparse, dim3(8192), dim3(256), 0, st, out, K, vtype, value_stride, first, key_space, nrec,
-                       s0, pa, pc);
-    return hipGetLastError();
-}
-
-__global__ void k_synth_fill(int vtype, void* p, int64_t n, uint64_t s0) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t h = splitmix64_dev(s0 + (uint64_t)i);
-        if (vtype == kF32) ((float*)p)[i] = (float)((int32_t)(h % 100) - 50) * 0x1p-17f;
-        else if (vtype == kF64) ((double*)p)[i] = (double)((int32_t)(h % 100) - 50) * 0x1p-17;
-        else ((int32_t*)p)[i] = 64 + (int32_t)(h % 51);
-    }
-}
-// Streaming ceilings (diagnostic): 4 independent 16-B nt loads per lane in
-// flight, contiguous 4 KiB per wave step. COPY writes what it reads; READ folds
-// the loads into one word that is stored only if it hits a sentinel.
-template <bool COPY>
-__global__ __launch_bounds__(256) void k_stream(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src,
-                                                int64_t n16) {
-    const int64_t lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    uint32_t fold = 0;
-    for (int64_t base = wave * 256; base < n16; base += nwaves * 256) {
-        u32x4 v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t i = base + j * 64 + lane;
-            v[j] = ldg16_nt(src + (i < n16 ? i : 0) * 16);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t i = base + j * 64 + lane;
-            if constexpr (COPY) {
-                if (i < n16) stg16(dst + i * 16, v[j]);
-            } else {
-                fold ^= v[j].x ^ v[j].y ^ v[j].z ^ v[j].w;
-            }
-        }
-    }
-    if constexpr (!COPY)
-        if (fold == 0x9E3779B9u) *(uint32_t*)dst = fold;
-}
-
-// Ring reduce-scatter footprint (diagnostic, bench.py --emulate-rs): the local HBM
-// traffic of one rank's ring reduce-scatter, as ONE kernel of `channels` blocks
-// (RCCL runs one persistent block per channel). world - 1 steps: step s reads the
-// chunk the rank sends, (rank - s - 1) mod world, plus the chunk that arrived at
-// step s - 1, and writes their sum where the next rank's write would land (a local
-// stand-in for the peer's write into this rank's buffer); the last step adds the
-// rank's own chunk into recv. A thread owns the same vectors in every step, so the
-// steps need no synchronization. Values are meaningless (no peer contributes).
-template <typename T>
-__global__ __launch_bounds__(256) void k_ring_rs(const T* __restrict__ part, T* __restrict__ recv,
-                                                 T* __restrict__ land, int64_t chunk16, int world, int rank) {
-    constexpr int VEC = Elem<T>::VEC, U = 8;  // 8 vectors per thread per step in flight, as RCCL's unrolled copies
-    const uint8_t* P = (const uint8_t*)part;
-    uint8_t* Lb[2] = {(uint8_t*)land, (uint8_t*)land + chunk16 * 16};
-    const int64_t nthr = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < chunk16; i0 += nthr * U) {
-        for (int s2 = 0; s2 < world; ++s2) {
-            const int64_t c = s2 == world - 1 ? rank : ((rank - s2 - 1) % world + world) % world;
-            u32x4 xa[U], ya[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t i = i0 + u * nthr;
-                xa[u] = i < chunk16 ? ldg16_nt(P + (c * chunk16 + i) * 16) : u32x4{0u, 0u, 0u, 0u};
-                ya[u] = (s2 > 0 && i < chunk16) ? ldg16_nt(Lb[s2 & 1] + i * 16) : u32x4{0u, 0u, 0u, 0u};
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t i = i0 + u * nthr;
-                if (i >= chunk16) continue;
-                T x[VEC], y[VEC];
-                unpack<T>(xa[u], x);
-                unpack<T>(ya[u], y);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) x[e] = Elem<T>::add(x[e], y[e]);
-                stg16_nt((s2 == world - 1 ? (uint8_t*)recv : Lb[(s2 + 1) & 1]) + i * 16, pack<T>(x));
-            }
-        }
-    }
-}
-
-hipError_t launch_ring_rs(int vtype, const void* part, void* recv, void* land, int64_t chunk_bytes, int world,
-                          int rank, int channels, hipStream_t st) {
-    const int64_t n16 = chunk_bytes / 16;
-    if (n16 <= 0) return hipSuccess;
-    const dim3 g((unsigned)std::max(1, channels)), blk(256);
-    if (vtype == kF64)
-        hipLaunchKernelGGL(k_ring_rs<double>, g, blk, 0, st, (const double*)part, (double*)recv, (double*)land, n16,
-                           world, rank);
-    else if (vtype == kI32)
-        hipLaunchKernelGGL(k_ring_rs<int32_t>, g, blk, 0, st, (const int32_t*)part, (int32_t*)recv, (int32_t*)land,
-                           n16, world, rank);
-    else
-        hipLaunchKernelGGL(k_ring_rs<float>, g, blk, 0, st, (const float*)part, (float*)recv, (float*)land, n16,
-                           world, rank);
-    return hipGetLastError();
-}
-
-// Random-RMW floor (diagnostic): one plain 4-B read-modify-write per update over a
-// globally sorted index list — the best case of config 3's scatter-add (every update
-// in address order, no partition), against which the leaf kernel is judged.
-// Repeated indices race: the array's values are not meaningful afterwards.
-__global__ __launch_bounds__(256) void k_rmw_floor(float* __restrict__ a, const uint32_t* __restrict__ idx,
-                                                   const float* __restrict__ v, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t k = idx[i];
-        a[k] = a[k] + v[i];
-    }
-}
-
-hipError_t launch_rmw_floor(float* a, const uint32_t* idx, const float* v, int64_t n, hipStream_t st, LaunchEv ev) {
-    if (n <= 0) return hipSuccess;
-    // one update per thread up to 2^28 updates (config 3: 32e6), grid-stride beyond
-    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)1 << 20);
-    return launch_k(k_rmw_floor, dim3(grid), dim3(256), 0, st, ev, a, idx, v, n);
-}
-
-// Row-gather floor (diagnostic, config 5): the touched rows of an int32 shard in row
-// order, each read once, every record that lists it (listed in push order by the
-// caller, `addr` = the record's value bytes) gathered and added, the row written once
-// — the same bytes as the IntMatrixStore reduce with no key index, slot table,
-// negativity check or error bookkeeping. One wave per touched row (<= 256 16-B
-// vectors: cols <= 1024), four records' loads in flight, XCD-contiguous blocks as the
-// product's DEPTH-3 reduce. The values are meaningful (plain wrapping int adds).
-__global__ __launch_bounds__(256) void k_gather_floor(int32_t* __restrict__ shard, int32_t cols,
-                                                      const int32_t* __restrict__ trow, const int32_t* __restrict__ tptr,
-                                                      const uint64_t* __restrict__ addr, int64_t ntouched) {
-    const int64_t w = xcd_block() * 4 + (threadIdx.x >> 6);
-    if (w >= ntouched) return;
-    const int lane = threadIdx.x & 63, nvec = cols / 4;
-    uint8_t* rowp = (uint8_t*)(shard + (int64_t)trow[w] * cols);
-    const int32_t b0 = tptr[w], b1 = tptr[w + 1];
-    u32x4 acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int v = lane + 64 * j;
-        acc[j] = v < nvec ? ldg16_nt(rowp + v * 16) : u32x4{0u, 0u, 0u, 0u};
-    }
-    for (int32_t e = b0; e < b1; e += 4) {
-        u32x4 x[4][4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint64_t a = e + k < b1 ? uni64(addr[e + k]) : 0ull;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int v = lane + 64 * j;
-                x[k][j] = (a && v < nvec) ? ldg16_nt((const uint8_t*)a + v * 16) : u32x4{0u, 0u, 0u, 0u};
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] += x[k][j];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int v = lane + 64 * j;
-        if (v < nvec) stg16_nt(rowp + v * 16, acc[j]);
-    }
-}
-
-hipError_t launch_gather_floor(int32_t* shard, int32_t cols, const int32_t* trow, const int32_t* tptr,
-                               const uint64_t* addr, int64_t ntouched, hipStream_t st, LaunchEv ev) {
-    if (ntouched <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)((ntouched + 3) / 4);
-    return launch_k(k_gather_floor, dim3(grid), dim3(256), 0, st, ev, shard, cols, trow, tptr, addr, ntouched);
-}
-
-// Dense stream floor (diagnostic, config 4 and its AdaGrad variant): the shard's
-// elements in order, each read once with the same element of every full-range push
-// whose records are rows in order (record r = row r, values 4 bytes after the key),
-// summed in push order and written once — to `out` (the speculative second buffer,
-// as k_flat_ident writes it) or in place; ADA: delta += u·u beside it (AdaGrad's
-// data / delta stream, k_ada_ident's bytes). No key checks, slot tables or maxDelta
-// bookkeeping: the plain stream of the same bytes, over the same allocations.
-template <bool ADA>
-__global__ __launch_bounds__(256) void k_dense_floor(const float* __restrict__ data, float* __restrict__ out,
-                                                     float* __restrict__ delta, Batch bt, int nb, int64_t stride,
-                                                     int K, int32_t cols, int64_t nvec) {
-    constexpr int U = 2, D = 4;
-    const int64_t v0 = xcd_block() * (256 * U) + threadIdx.x;
-    int64_t off[U];
-    bool ok[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t v = v0 + u * 256, e = v * 4;
-        ok[u] = v < nvec;
-        off[u] = (e / cols) * stride + K + (e % cols) * 4;
-    }
-    u32x4 acc[U], dl[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t v = v0 + u * 256;
-        acc[u] = ok[u] ? ldg16_nt((const uint8_t*)data + v * 16) : u32x4{0u, 0u, 0u, 0u};
-        if (ADA) dl[u] = ok[u] ? ldg16_nt((const uint8_t*)delta + v * 16) : u32x4{0u, 0u, 0u, 0u};
-    }
-    for (int b = 0; b < nb; b += D) {
-        u32x4 x[D][U];
-#pragma unroll
-        for (int d = 0; d < D; ++d)
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-                x[d][u] = (b + d < nb && ok[u]) ? ldg16_nt(bt.base[b + d] + off[u]) : u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            if (b + d >= nb) break;
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float g = __uint_as_float(x[d][u][e]);
-                    acc[u][e] = __float_as_uint(__fadd_rn(__uint_as_float(acc[u][e]), g));
-                    if (ADA) dl[u][e] = __float_as_uint(__fadd_rn(__uint_as_float(dl[u][e]), __fmul_rn(g, g)));
-                }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        if (!ok[u]) continue;
-        const int64_t v = v0 + u * 256;
-        stg16_nt((uint8_t*)out + v * 16, acc[u]);
-        if (ADA) stg16_nt((uint8_t*)delta + v * 16, dl[u]);
-    }
-}
-
-hipError_t launch_dense_floor(const float* data, float* out, float* delta, const Batch& bt, int nb, int64_t stride,
-                              int K, int32_t cols, int64_t elems, hipStream_t st, LaunchEv ev) {
-    const int64_t nvec = elems / 4;
-    if (nvec <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)((nvec + 511) / 512);
-    return launch_k(delta ? k_dense_floor<true> : k_dense_floor<false>, dim3(grid), dim3(256), 0, st, ev, data, out,
-                    delta, bt, nb, stride, K, cols, nvec);
-}
-
-hipError_t launch_stream(bool copy, void* dst, const void* src, int64_t n16, hipStream_t st, LaunchEv ev) {
-    if (n16 <= 0) return hipSuccess;
-    const int64_t want = (n16 + 1023) / 1024;  // one 256-thread block per 4 wave steps
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, 256 * 16));
-    return launch_k(copy ? k_stream<true> : k_stream<false>, dim3(grid), dim3(256), 0, st, ev, (uint8_t*)dst,
-                    (const uint8_t*)src, n16);
-}
-
-// DataStore.rand() distributions (dml_store_rand). f32: (a/100f - 0.5f)/cols,
-// a uniform in 0..99, float arithmetic as in FloatMatrixStore.java:46-47.
-// f64: one thread per row, |N(0,1)| (Box-Muller) then the row over its L2 norm
-// (DoubleMatrixStore.java:196-206).
-__global__ void k_rand_f32(float* p, int64_t n, int32_t cols, uint64_t s0) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int a = (int)(splitmix64_dev(s0 + (uint64_t)i) % 100u);
-        p[i] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)a, 100.0f), 0.5f), (float)cols);
-    }
-}
-__device__ inline double rand_abs_gauss(uint64_t h) {
-    const double u1 = (double)((h >> 11) + 1) * 0x1p-53;                   // (0, 1]
-    const double u2 = (double)(splitmix64_dev(h) >> 11) * 0x1p-53;          // [0, 1)
-    return fabs(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
-}
-__global__ void k_rand_f64_rows(double* p, int64_t rows, int32_t cols, uint64_t s0) {
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
-        double* row = p + r * cols;
-        double sum = 0.0;
-        for (int32_t j = 0; j < cols; ++j) {
-            const double g = rand_abs_gauss(splitmix64_dev(s0 + (uint64_t)(r * cols + j)));
-            row[j] = g;
-            sum = __dadd_rn(sum, __dmul_rn(g, g));
-        }
-        sum = sqrt(sum);
-        for (int32_t j = 0; j < cols; ++j) row[j] = __ddiv_rn(row[j], sum);
-    }
-}
-hipError_t launch_rand(int vtype, void* p, int64_t rows, int32_t cols, uint64_t s0, hipStream_t st) {
-    if (rows <= 0) return hipSuccess;
-    if (vtype == kF32) hipLaunchKernelGGL(k_rand_f32, dim3(grid_for(rows * cols)), dim3(256), 0, st, (float*)p, rows * cols, cols, s0);
-    else if (vtype == kF64) hipLaunchKernelGGL(k_rand_f64_rows, dim3(grid_for(rows)), dim3(256), 0, st, (double*)p, rows, cols, s0);
-    return hipGetLastError();
-}
-
-hipError_t launch_synth_fill(int vtype, void* p, int64_t n, uint64_t s0, hipStream_t st) {
-    hipLaunchKernelGGL(k_synth_fill, dim3(8192), dim3(256), 0, st, vtype, p, n, s0);
-    return hipGetLastError();
-}
-
-// Row index of every record of one push (-1 outside the shard): the host's
-// duplicate-row replay reads these to split the push into unique-row layers.
-__global__ void k_key_rows(const uint8_t* __restrict__ base, int64_t nrec, int64_t stride, int K, int64_t first,
-                           int64_t rows, int32_t* __restrict__ out) {
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrec; r += (int64_t)gridDim.x * blockDim.x)
-        out[r] = (int32_t)row_index(ld_key(base + r * stride, K), first, rows);
-}
-hipError_t launch_key_rows(const uint8_t* base, int64_t nrec, int64_t stride, int K, int64_t first, int64_t rows,
-                           int32_t* out, hipStream_t st) {
-    if (nrec <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_key_rows, dim3(grid_for(nrec)), dim3(256), 0, st, base, nrec, stride, K, first, rows, out);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Two-moment AdaGrad reduce-scatter: the sharded
-// AdaGrad path whose xGMI bytes do not grow with the pushes per rank. Each rank
-// pre-reduces its full-range pushes into Σu and Σu·u per element (fp32, push
-// order; u·u rounded, then added, like the reference's delta update,
-// FloatMatrixStoreAdaGrad.java:265-267), written as one [row][2 x cols] run so a
-// rank's share of both is one contiguous reduce-scatter chunk; the owner applies
-// row += Σu, delta += Σu², and alpha = f(final delta) where it ends above 1
-// (:268-272: delta never falls, so the last push that sets alpha sees the final
-// delta). The summation order is not the reference's: within 1e-6, not bit-exact.
-//
-// k_moments_flat: k_reduce_flat's layout (R rows per wave as one flat run of
-// 16-B vectors), slot rows in LDS unless every push is identity (Batch::ident_ok).
-// A call whose index met a key outside the matrix or a repeated row writes zeros
-// (dml_prereduce_end reports the error; nothing of it is applied).
-template <int JMAX>
-__global__ __launch_bounds__(256) void k_moments_flat(int64_t ntask, int32_t cols, int32_t R, const Batch bt, int nb,
-                                                      int64_t stride, int K, int32_t* __restrict__ slot,
-                                                      const Ctrl* __restrict__ ctrl, RowMap rm) {
-    constexpr int VEC = 4;
-    constexpr int RMAX = 16;
-    __shared__ int32_t s_slot[4][RMAX * kMaxW];
-    const int lane = threadIdx.x & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t t0 = (xcd_block() * 4 + wid) * R;  // first task row of the wave (XCD-contiguous, as k_reduce_flat)
-    if (t0 >= ntask) return;
-    const int NV = cols / VEC;
-    const int nrow = (int)(ntask - t0 < (int64_t)R ? ntask - t0 : (int64_t)R);
-    const int ss = slot_stride(nb);
-    int32_t* const ls = s_slot[wid];
-    const uint64_t ident = bt.ident_ok ? ctrl->ident : 0ull;
-    const uint64_t nbm = nb >= 64 ? ~0ull : (1ull << nb) - 1ull;
-    const bool all_id = (ident & nbm) == nbm;
-    const bool err = ctrl->cutoff != kNoPos || ctrl->no_dup == 0u;
-    const int64_t lrow = rm.row(t0 + lane);
-    const uint32_t padm = (uint32_t)__ballot(lane < nrow && lrow >= rm.rows_total);
-    if (!all_id) {
-        // slot rows into LDS, handed back clean (-1) like k_reduce_flat's
-        for (int e = lane; e < nrow * nb; e += 64) {
-            const int rl = e / nb, b = e - rl * nb;
-            const int64_t mr = rm.row(t0 + rl);
-            int32_t v = -1;
-            if (!((padm >> rl) & 1u)) {
-                if ((ident >> b) & 1ull) {
-                    v = mr < bt.nrec[b] ? (int32_t)mr : -1;
-                } else {
-                    v = slot[mr * ss + b];
-                    if (v >= 0) slot[mr * ss + b] = -1;
-                }
-            }
-            ls[rl * kMaxW + b] = v;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    int rc[JMAX];
-    uint32_t on = 0;
-    float acc[JMAX][VEC], sq[JMAX][VEC];
-    const int nvec = nrow * NV;
-#pragma unroll
-    for (int j = 0; j < JMAX; ++j) {
-        const int v = j * 64 + lane;
-        const int rlj = v < nvec ? v / NV : 0;
-        const int cvj = v < nvec ? v - rlj * NV : 0;
-        rc[j] = (rlj << 16) | cvj;
-        on |= ((v < nvec && !((padm >> rlj) & 1u) && !err) ? 1u : 0u) << j;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) acc[j][e] = sq[j][e] = 0.f;
-    }
-#pragma unroll 1
-    for (int b = 0; b < nb; ++b) {
-        const uint8_t* const bp = bt.base[b];
-        int32_t rr[JMAX];
-        u32x4 raw[JMAX];
-#pragma unroll
-        for (int j = 0; j < JMAX; ++j) {
-            const int rl = rc[j] >> 16;
-            rr[j] = (on >> j & 1u) ? (all_id ? (int32_t)rm.row(t0 + rl) : ls[rl * kMaxW + b]) : -1;
-            raw[j] = rr[j] >= 0 ? ldg16_nt(bp + (int64_t)rr[j] * stride + K + (int64_t)(rc[j] & 0xFFFF) * 16)
-                                : u32x4{0u, 0u, 0u, 0u};
-        }
-#pragma unroll
-        for (int j = 0; j < JMAX; ++j) {
-            if (rr[j] < 0) continue;
-            float u[VEC];
-            unpack<float>(raw[j], u);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                acc[j][e] = __fadd_rn(acc[j][e], u[e]);
-                sq[j][e] = __fadd_rn(sq[j][e], __fmul_rn(u[e], u[e]));
-            }
-        }
-    }
-    float* const out = (float*)rm.out;
-#pragma unroll
-    for (int j = 0; j < JMAX; ++j) {
-        if (j * 64 + lane >= nvec) continue;
-        float* const op = out + (t0 + (rc[j] >> 16)) * (int64_t)(2 * cols) + (rc[j] & 0xFFFF) * VEC;
-        stg16(op, pack<float>(acc[j]));
-        stg16(op + cols, pack<float>(sq[j]));
-    }
-}
-
-hipError_t launch_moments(int64_t ntask, int32_t cols, const Batch& bt, int nb, int64_t stride, int K, int32_t* slot,
-                          const Ctrl* ctrl, RowMap rm, hipStream_t st, LaunchEv ev) {
-    constexpr int JMAX = 8;
-    if (!vec_geom(kF32).flat_row(cols) || !rm.out) return hipErrorInvalidValue;  // the flat shapes
-    const int R = rows_per_wave(JMAX, cols / 4);
-    const int64_t nblocks = flat_blocks(ntask, R, 4);
-    if (nblocks <= 0) return hipSuccess;
-    g_kernel_name = "dml::k_moments_flat<8>";
-    return launch_k(k_moments_flat<JMAX>, dim3((unsigned)nblocks), dim3(256), 0, st, ev, ntask, cols, R, bt, nb,
-                    stride, K, slot, ctrl, rm);
-}
-
-// Owner apply of the reduce-scattered moments ([row][Σu | Σu²], rows x 2 cols):
-// data += Σu, delta += Σu², alpha = f(delta) where delta ends above 1, each
-// element's strict rise of delta its maxDelta candidate (ties: first in row-major
-// order). One candidate per block into ada.cand.
-__global__ __launch_bounds__(256) void k_ada_moments(float* __restrict__ shard, const float* __restrict__ src,
-                                                     int64_t rows, int32_t cols, AdaArgs ada) {
-    const int NV = cols / 4;
-    const int64_t nvec = rows * NV;
-    float cand_v = 0.f;
-    uint64_t cand_p = kNoPos;
-    bool cand_ok = false;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t r = i / NV;
-        const int cv = (int)(i - r * NV);
-        const int64_t ei = r * cols + cv * 4;
-        const float* sp = src + r * (int64_t)(2 * cols) + cv * 4;
-        float a[4], d[4], su[4], s2[4];
-        unpack<float>(ldg16_nt((const uint8_t*)(shard + ei)), a);
-        unpack<float>(ldg16_nt((const uint8_t*)(ada.delta + ei)), d);
-        unpack<float>(ldg16((const uint8_t*)sp), su);
-        unpack<float>(ldg16((const uint8_t*)(sp + cols)), s2);
-        float na[4];
-        bool all_a = true;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            a[e] = __fadd_rn(a[e], su[e]);
-            const float nd = __fadd_rn(d[e], s2[e]);
-            if (nd > d[e] && (!cand_ok || nd > cand_v)) {  // elements visited in row-major order per thread
-                cand_ok = true;
-                cand_v = nd;
-                cand_p = (uint64_t)(ei + e);
-            }
-            d[e] = nd;
-            na[e] = 0.f;
-            if (nd > 1.0f) {
-                na[e] = (float)((double)ada.initial_alpha / ((double)ada.factor * sqrt((double)nd)));
-                if (na[e] < ada.min_alpha) na[e] = ada.min_alpha;
-            } else {
-                all_a = false;
-            }
-        }
-        stg16_nt(shard + ei, pack<float>(a));
-        stg16_nt(ada.delta + ei, pack<float>(d));
-        if (all_a) {
-            stg16_nt(ada.alpha + ei, pack<float>(na));
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (d[e] > 1.0f) ada.alpha[ei + e] = na[e];
-        }
-    }
-    cand_block_best<4>(cand_ok, cand_v, cand_p);
-    if (threadIdx.x == 0) {
-        DeltaCand c;
-        c.value = cand_v;
-        c.valid = cand_ok;
-        c.pos = cand_p;
-        ada.cand[blockIdx.x] = c;
-    }
-}
-
-// maxDelta finalize for element-index candidates (k_ada_moments): the reference's
-// strict `>` against the running maximum; row = the element's key (first + row).
-__global__ __launch_bounds__(256) void k_maxdelta_elems(const DeltaCand* __restrict__ cand, int64_t n,
-                                                        MaxDelta* __restrict__ md, int64_t first, int32_t cols) {
-    bool ok = false;
-    float v = 0.f;
-    uint64_t p = kNoPos;
-    cand_scan(cand, threadIdx.x, n, 256, ok, v, p);
-    cand_block_best<4>(ok, v, p);
-    if (threadIdx.x != 0) return;
-    if (ok && v > md->value) {
-        md->value = v;
-        md->row = (int32_t)(first + (int64_t)(p / (uint64_t)cols));
-        md->col = (int32_t)(p % (uint64_t)cols);
-    }
-}
-
-hipError_t launch_ada_moments(float* shard, const float* src, int64_t rows, int32_t cols, const AdaArgs& ada,
-                              MaxDelta* md, int64_t first, hipStream_t st, LaunchEv ev) {
-    if (cols % 4 || rows <= 0) return hipErrorInvalidValue;
-    g_kernel_name = "dml::k_ada_moments";
-    const hipError_t e = launch_k(k_ada_moments, dim3(kMomentBlocks), dim3(256), 0, st, ev, shard, src, rows, cols, ada);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_maxdelta_elems, dim3(1), dim3(256), 0, st, ada.cand, (int64_t)kMomentBlocks, md, first, cols);
-    return hipGetLastError();
-}
-
-
-// ---------------------------------------------------------------------------
-// Chained reduce-scatter step of an AdaGrad matrix (dml_prereduce_chain_piece_ada,
-// DESIGN.md §6): the slice travels as two planes, data and delta, plus one 4-byte
-// touched mark per row. Task row t starts from base + t*cols in both planes; the
-// handle's pushes' records of its model row are added in push order with the
-// arithmetic of k_ada_ident / k_ada_flat (acc = acc + g, nd = dl + g*g, one IEEE
-// rounding each), and both planes are written to the outputs (out == base works:
-// every element and every mark is read and written by one lane). All pushes of the
-// handle (up to 64) go through one pass: the planes are read once and written once
-// whatever the push count, D push loads in flight per lane. No alpha is read or
-// written: the owner computes it once from the delta that comes home
-// (k_chain_ada_commit). An element's last strict rise of delta is its maxDelta
-// candidate, reduced per block (max value, then lowest position) into ca.cand; a
-// handle's pushes are numbered by column (dml_prereduce_begin: bidx[j] = j), so a
-// candidate's position is formed from its push column. A row no push lists, a
-// padding row, and every row of a handle whose index failed (ctrl_index_failed,
-// read by every wave) are copied bit for bit, marks included; a listed row of a
-// good handle sets its mark.
-//
-// k_chain_ada_ident: the vector stream for calls the host has seen to be all
-// identity (ascending full-range pushes of a flat width, every key checked by
-// k_ident_full before the first piece: config 4's shape). A thread owns one 16-B
-// vector of the task planes; its model row goes through the row map per vector, so
-// row blocks of any size work.
-template <int D>
-__global__ __launch_bounds__(256) void k_chain_ada_ident(int64_t nvec, int32_t cols, const Batch bt, int nb,
-                                                         int64_t stride, int K, const Ctrl* __restrict__ ctrl,
-                                                         RowMap rm, ChainAda ca) {
-    constexpr int VEC = 4;
-    const int64_t v = xcd_block() * 256 + threadIdx.x;
-    const bool on = v < nvec;
-    const int64_t e0 = on ? v * VEC : 0;
-    const int64_t t = e0 / cols;
-    const int c = (int)(e0 - t * cols);
-    const int64_t mr = rm.row(t);
-    const bool live = on && mr < rm.rows_total && !ctrl_index_failed(ctrl);
-    const int64_t roff = mr * stride + K + (int64_t)c * 4;
-    const u32x4 z{0u, 0u, 0u, 0u};
-    float acc[VEC], dl[VEC], rv[VEC];
-    int rb[VEC];  // push of the element's last strict rise (-1: none)
-    unpack<float>(on ? ldg16_nt((const uint8_t*)rm.base + e0 * 4) : z, acc);
-    unpack<float>(on ? ldg16_nt((const uint8_t*)ca.base_delta + e0 * 4) : z, dl);
-    uint32_t mark = 0u;
-    if (on && c == 0 && ca.base_marks) mark = ca.base_marks[t];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        rv[e] = 0.f;
-        rb[e] = -1;
-    }
-#pragma unroll 1
-    for (int b0 = 0; b0 < nb; b0 += D) {
-        u32x4 raw[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            const int b = b0 + d < nb ? b0 + d : b0;
-            raw[d] = live && b0 + d < nb ? ldg16_nt(bt.base[b] + roff) : z;
-        }
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            if (b0 + d >= nb || !live) continue;
-            float g[VEC];
-            unpack<float>(raw[d], g);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                acc[e] = __fadd_rn(acc[e], g[e]);
-                const float nd = __fadd_rn(dl[e], __fmul_rn(g[e], g[e]));
-                if (nd > dl[e]) { rv[e] = nd; rb[e] = b0 + d; }
-                dl[e] = nd;
-            }
-        }
-    }
-    float cand_v = 0.f;
-    uint64_t cand_p = kNoPos;
-    bool cand_ok = false;
-    if (on) {
-        stg16_nt((uint8_t*)rm.out + e0 * 4, pack<float>(acc));
-        stg16_nt((uint8_t*)ca.out_delta + e0 * 4, pack<float>(dl));
-        if (c == 0) ca.out_marks[t] = live ? 1u : mark;
-        // (push, element) order is position order inside the thread's vector
-        int key = 0;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            if (rb[e] < 0) continue;
-            const int k = (rb[e] << 2) | e;
-            if (!cand_ok || rv[e] > cand_v || (rv[e] == cand_v && k < key)) {
-                cand_ok = true;
-                cand_v = rv[e];
-                key = k;
-            }
-        }
-        if (cand_ok) cand_p = pos_of((uint64_t)(key >> 2), (uint64_t)(roff + (key & 3) * 4));
-    }
-    cand_block_best<4>(cand_ok, cand_v, cand_p);
-    if (threadIdx.x == 0) {
-        DeltaCand cd;
-        cd.value = cand_v;
-        cd.valid = cand_ok;
-        cd.pos = cand_p;
-        ca.cand[blockIdx.x] = cd;
-    }
-}
-
-// k_chain_ada_rows: the slot-table shape for everything else (permuted pushes, ragged
-// or narrow rows, rows no push lists): one wave per task row, its lanes over the
-// row's columns 64 at a time, element by element (any width, 4-byte aligned records).
-// The row's slots (one per push; slot = row for a push k_ident_full confirmed) are
-// read once into LDS and handed back clean (-1), as the pre-reduce kernels do.
-template <int D>
-__global__ __launch_bounds__(256) void k_chain_ada_rows(int64_t ntask, int32_t cols, const Batch bt, int nb,
-                                                        int64_t stride, int K, int32_t* __restrict__ slot,
-                                                        const Ctrl* __restrict__ ctrl, RowMap rm, ChainAda ca) {
-    __shared__ int32_t s_slot[4][kMaxW];
-    const int lane = threadIdx.x & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t t = (int64_t)blockIdx.x * 4 + wid;
-    const bool on = t < ntask;
-    const int64_t mr = on ? rm.row(t) : 0;
-    const bool good = on && mr < rm.rows_total && !ctrl_index_failed(ctrl);
-    const uint64_t ident = bt.ident_ok ? ctrl->ident : 0ull;
-    const int ss = slot_stride(nb);
-    int32_t* const ls = s_slot[wid];
-    int32_t sl = -1;
-    if (good && lane < nb) {
-        if ((ident >> lane) & 1ull) {
-            sl = (int32_t)mr;  // a confirmed push is full-range: record r is row r
-        } else {
-            sl = slot[mr * ss + lane];
-            if (sl >= 0) slot[mr * ss + lane] = -1;
-        }
-    }
-    ls[lane] = sl;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const bool live = __ballot(sl >= 0) != 0ull;  // some push lists the row
-    float cand_v = 0.f;
-    uint64_t cand_p = kNoPos;
-    bool cand_ok = false;
-    const float* const bd = (const float*)rm.base;
-    float* const od = (float*)rm.out;
-    for (int c0 = 0; c0 < cols; c0 += 64) {
-        const int c = c0 + lane;
-        const bool act = on && c < cols;
-        const int64_t i = act ? t * (int64_t)cols + c : 0;
-        float acc = 0.f, dl = 0.f, rv = 0.f;
-        int rb = -1;
-        if (act) {
-            acc = bd[i];
-            dl = ca.base_delta[i];
-        }
-        if (live) {
-#pragma unroll 1
-            for (int b0 = 0; b0 < nb; b0 += D) {
-                int32_t s[D];
-                float g[D];
-#pragma unroll
-                for (int d = 0; d < D; ++d) {
-                    const int b = b0 + d < nb ? b0 + d : b0;
-                    s[d] = b0 + d < nb ? __builtin_amdgcn_readfirstlane(ls[b]) : -1;
-                    g[d] = act && s[d] >= 0
-                               ? Elem<float>::load(bt.base[b] + (int64_t)s[d] * stride + K + (int64_t)c * 4)
-                               : 0.f;
-                }
-#pragma unroll
-                for (int d = 0; d < D; ++d) {
-                    if (s[d] < 0 || !act) continue;
-                    acc = __fadd_rn(acc, g[d]);
-                    const float nd = __fadd_rn(dl, __fmul_rn(g[d], g[d]));
-                    if (nd > dl) { rv = nd; rb = b0 + d; }
-                    dl = nd;
-                }
-            }
-        }
-        if (act) {
-            od[i] = acc;
-            ca.out_delta[i] = dl;
-            if (rb >= 0) {
-                const uint64_t p = pos_of((uint64_t)rb, (uint64_t)((int64_t)ls[rb] * stride + K + (int64_t)c * 4));
-                if (cand_better(true, rv, p, cand_ok, cand_v, cand_p)) {
-                    cand_ok = true;
-                    cand_v = rv;
-                    cand_p = p;
-                }
-            }
-        }
-    }
-    if (on && lane == 0) ca.out_marks[t] = live ? 1u : (ca.base_marks ? ca.base_marks[t] : 0u);
-    cand_block_best<4>(cand_ok, cand_v, cand_p);
-    if (threadIdx.x == 0) {
-        DeltaCand cd;
-        cd.value = cand_v;
-        cd.valid = cand_ok;
-        cd.pos = cand_p;
-        ca.cand[blockIdx.x] = cd;
-    }
-}
-
-constexpr int kChainAdaD = 8;  // push loads in flight per lane
-
-int64_t chain_ada_blocks(bool ident, int64_t ntask, int32_t cols) {
-    return ident ? (ntask * (cols / 4) + 255) / 256 : (ntask + 3) / 4;
-}
-
-hipError_t launch_chain_ada(bool ident, int64_t ntask, int32_t cols, const Batch& bt, int nb, int64_t stride, int K,
-                            int32_t* slot, const Ctrl* ctrl, RowMap rm, const ChainAda& ca, hipStream_t st,
-                            int64_t* ncand_out, LaunchEv ev) {
-    if (!rm.base || !rm.out || !ca.base_delta || !ca.out_delta || !ca.out_marks || !ca.cand)
-        return hipErrorInvalidValue;
-    if (ident && (cols % 4 || nb <= 0)) return hipErrorInvalidValue;
-    const int64_t nblocks = chain_ada_blocks(ident, ntask, cols);
-    if (ncand_out) *ncand_out = nblocks;
-    if (nblocks <= 0) return hipSuccess;
-    if (nblocks > INT32_MAX) return hipErrorInvalidValue;
-    constexpr int D = kChainAdaD;
-    if (ident) {
-        static const std::string kn = kname("k_chain_ada_ident", D);
-        g_kernel_name = kn.c_str();
-        return launch_k(k_chain_ada_ident<D>, dim3((unsigned)nblocks), dim3(256), 0, st, ev, ntask * (cols / 4), cols,
-                        bt, nb, stride, K, ctrl, rm, ca);
-    }
-    static const std::string kn = kname("k_chain_ada_rows", D);
-    g_kernel_name = kn.c_str();
-    return launch_k(k_chain_ada_rows<D>, dim3((unsigned)nblocks), dim3(256), 0, st, ev, ntask, cols, bt, nb, stride, K,
-                    slot, ctrl, rm, ca);
-}
-
-// The owner's commit of its AdaGrad slice when the chain brings it home: shard data
-// and delta = the slice's; alpha = initialAlpha / (factor * sqrt(delta)), clamped to
-// minAlpha (k_ada_ident's expression, the owner's parameters), where the row's mark is
-// set and delta > 1 — inside one call delta never falls, so this is the alpha the
-// reference's last update of the element left (FloatMatrixStoreAdaGrad.java:268-272).
-// A NaN delta fails the comparison: such an element keeps the alpha the owner held
-// (the one documented divergence). The store's running maxDelta
-// becomes the travelling record.
-__global__ __launch_bounds__(256) void k_chain_ada_commit(float* __restrict__ data, float* __restrict__ delta,
-                                                          float* __restrict__ alpha, MaxDelta* __restrict__ md,
-                                                          const float* __restrict__ sdata,
-                                                          const float* __restrict__ sdelta,
-                                                          const uint32_t* __restrict__ marks,
-                                                          const MaxDelta* __restrict__ rec, int64_t n, int32_t cols,
-                                                          float initial_alpha, float min_alpha, float factor) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float d = sdelta[i];
-        data[i] = sdata[i];
-        delta[i] = d;
-        if (d > 1.0f && marks[i / cols] != 0u) {
-            float a = (float)((double)initial_alpha / ((double)factor * sqrt((double)d)));
-            if (a < min_alpha) a = min_alpha;
-            alpha[i] = a;
-        }
-    }
-    if (md && blockIdx.x == 0 && threadIdx.x == 0) {
-        md->value = rec->value;
-        md->row = rec->row;
-        md->col = rec->col;
-    }
-}
-
-hipError_t launch_chain_ada_commit(float* data, float* delta, float* alpha, MaxDelta* md, const float* sdata,
-                                   const float* sdelta, const uint32_t* marks, const MaxDelta* rec, int64_t rows,
-                                   int32_t cols, const AdaArgs& ada, hipStream_t st) {
-    const int64_t n = rows * cols;
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192));
-    hipLaunchKernelGGL(k_chain_ada_commit, dim3(grid), dim3(256), 0, st, data, delta, alpha, md, sdata, sdelta, marks,
-                       rec, n, cols, ada.initial_alpha, ada.min_alpha, ada.factor);
     return hipGetLastError();
 }
 
