@@ -122,6 +122,8 @@ SIGNATURES = {
     "dml_coalescer_destroy": (None, [_vp]),
     "dml_coalesce_device": (C.c_int, [_vp, _P(dml_desc), _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _P(_i64), _vp]),
     "dml_diag_coalesce_times": (C.c_int, [_vp, _P(C.c_float)]),
+    "dml_coalescer_set_long_min": (C.c_int, [_vp, _i64]),
+    "dml_diag_coalesce_route": (C.c_int, [_vp, _P(_i64)]),
     "dml_group_unique_id": (C.c_int, [_vp, _i32]),
     "dml_group_push_exchange": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
     "dml_group_push_moments": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
@@ -190,6 +192,10 @@ DML_CODEC_KNOB_LOADS = 2
 DML_COALESCE_BLOCK_KEYS = 1024
 DML_COALESCE_BATCH = 16
 DML_COALESCE_DEPTH = 4
+# ... and the long-segment path: default threshold, k_co_sum_long's tile rows and slice bytes
+DML_COALESCE_LONG_MIN = 512
+DML_COALESCE_LONG_TILE = 128
+DML_COALESCE_LONG_SLICE = 256
 
 
 class NativeLibraryMissing(RuntimeError):

@@ -1,5 +1,6 @@
 // dml_coalesce.hip — the device gradient coalescer (C-ABI dml_coalescer_create / _destroy,
-// dml_coalesce_device, dml_diag_coalesce_times).
+// dml_coalesce_device, dml_coalescer_set_long_min, dml_diag_coalesce_times / _route;
+// DESIGN.md §4.13).
 //
 // The reference worker fetches through a KeyList, a HashSet<Long> (KeyList.java:14-19,59-61),
 // and accumulates its update per key in a HashMap before SparseMatrix.push writes one record
@@ -24,18 +25,16 @@
 //                 issued before the first add, adds strictly in occurrence order.
 //   k_co_sum_narrow  rows under 16 bytes (arrays, 1-3 f32 / i32 columns, one f64): one lane per key
 //
-// The variant is chosen by the value type and the row width alone, so there is no knob.
+// A segment of the context's long_min occurrences and more is left out by both walks and
+// summed by dml_coalesce_long.hip's kernels instead: the same adds in the same order.
 #include <hipcub/hipcub.hpp>
 
-#include "distml_ps.h"
-#include "dml_fetch_line.h"
-#include "dml_host.h"
+#include "dml_coalesce_dev.h"
 
 using namespace dml;
 
 namespace {
 
-constexpr int kCoBlock = 256;
 constexpr int kCoKeysPerThread = 4;
 constexpr int kCoBlockKeys = kCoBlock * kCoKeysPerThread;
 constexpr int kCoBatch = 16;  // indices a group fetches at a time (a group of G < 16 lanes: G)
@@ -44,12 +43,8 @@ static_assert(kCoBlockKeys == DML_COALESCE_BLOCK_KEYS && kCoBatch == DML_COALESC
                   kCoDepth == DML_COALESCE_DEPTH && kCoBatch % kCoDepth == 0,
               "exported tile sizes");
 constexpr uint64_t kSignBit = 1ull << 63;  // signed order as unsigned order
-constexpr int64_t kCoSpanBytes = 1024;     // 64 lanes x 16 bytes
 constexpr int64_t kCoMaxBlocks = (int64_t)1 << 22;
-
-__device__ inline uint32_t ldg32_nt(const uint8_t* p) {
-    return __builtin_nontemporal_load((const DML_GLOBAL uint32_t*)(p));
-}
+constexpr int kRouteWord = 16;  // count_dev[16], [17]: long segments, their occurrences
 
 __global__ __launch_bounds__(kCoBlock) void k_co_pairs(const int64_t* __restrict__ keys, int64_t n,
                                                        uint64_t* __restrict__ kin, uint32_t* __restrict__ vin) {
@@ -123,7 +118,8 @@ __global__ __launch_bounds__(kCoBlock) void k_co_heads(const uint64_t* __restric
 }
 
 // One block: blockoff[0..nb) from counts to the exclusive running sum, carried from one
-// 256-count tile to the next; *count = the number of heads.
+// 256-count tile to the next; *count = the number of heads. It also clears the two route
+// words behind the count (kRouteWord) for the call's long-segment list.
 __global__ __launch_bounds__(kCoBlock) void k_co_offsets(uint32_t* __restrict__ blockoff, int64_t nb,
                                                          uint32_t* __restrict__ count) {
     __shared__ uint32_t wsum[kCoBlock / 64];
@@ -137,40 +133,11 @@ __global__ __launch_bounds__(kCoBlock) void k_co_offsets(uint32_t* __restrict__ 
         carry += total;
         __syncthreads();  // wsum is rewritten by the next tile
     }
-    if (threadIdx.x == 0) *count = carry;
-}
-
-// One add as the reference's JVM on x86-64 makes it: rounded once (the build has
-// -ffp-contract=off), and the NaN an invalid operation creates (Inf - Inf: neither operand
-// is one) is that platform's NEGATIVE quiet NaN, 0xFFC00000 / 0xFFF8000000000000, where
-// gfx950 would create the positive one. An operand's NaN passes through, quieted, as on both.
-__device__ inline float add_ref(float a, float x) {
-    const float r = __fadd_rn(a, x);
-    return (r != r && a == a && x == x) ? __uint_as_float(0xFFC00000u) : r;
-}
-__device__ inline double add_ref(double a, double x) {
-    const double r = __dadd_rn(a, x);
-    return (r != r && a == a && x == x) ? __longlong_as_double((long long)0xFFF8000000000000ull) : r;
-}
-
-// acc + x per element of one 16-byte vector; int32 wraps.
-template <typename T> __device__ inline u32x4 add_vec(u32x4 a, u32x4 x);
-template <> __device__ inline u32x4 add_vec<float>(u32x4 a, u32x4 x) {
-    u32x4 r;
-    r.x = __float_as_uint(add_ref(__uint_as_float(a.x), __uint_as_float(x.x)));
-    r.y = __float_as_uint(add_ref(__uint_as_float(a.y), __uint_as_float(x.y)));
-    r.z = __float_as_uint(add_ref(__uint_as_float(a.z), __uint_as_float(x.z)));
-    r.w = __float_as_uint(add_ref(__uint_as_float(a.w), __uint_as_float(x.w)));
-    return r;
-}
-template <> __device__ inline u32x4 add_vec<int32_t>(u32x4 a, u32x4 x) { return a + x; }
-template <> __device__ inline u32x4 add_vec<double>(u32x4 a, u32x4 x) {
-    const double lo = add_ref(Elem<double>::from_bits(a.x, a.y), Elem<double>::from_bits(x.x, x.y));
-    const double hi = add_ref(Elem<double>::from_bits(a.z, a.w), Elem<double>::from_bits(x.z, x.w));
-    const uint64_t l = (uint64_t)__double_as_longlong(lo), h = (uint64_t)__double_as_longlong(hi);
-    u32x4 r;
-    r.x = (uint32_t)l; r.y = (uint32_t)(l >> 32); r.z = (uint32_t)h; r.w = (uint32_t)(h >> 32);
-    return r;
+    if (threadIdx.x == 0) {
+        *count = carry;
+        count[kRouteWord] = 0;
+        count[kRouteWord + 1] = 0;
+    }
 }
 
 struct SumP {
@@ -182,6 +149,7 @@ struct SumP {
     int64_t rowbytes;       // >= 16
     int64_t nspan;          // 1-KiB spans of a row
     int32_t lgG;            // log2 of the lanes of a group
+    uint32_t lmin;          // a segment of lmin occurrences and more is the long path's
 };
 
 // The sum starts at +0.0 and a sum of IEEE adds that starts there is never -0.0 (x + y is
@@ -218,6 +186,8 @@ __global__ __launch_bounds__(kCoBlock) void k_co_sum(const SumP a) {
             s = a.seg[u];
             e = u + 1 < a.m ? a.seg[u + 1] : (uint32_t)a.n;
         }
+        const bool lng = e - s >= a.lmin;  // the long path's: no walk and no store
+        if (lng) e = s;
         u32x4 acc = zero;
         for (uint32_t base = s; base < e; base += (uint32_t)B) {
             const int cnt = e - base < (uint32_t)B ? (int)(e - base) : B;
@@ -245,7 +215,7 @@ __global__ __launch_bounds__(kCoBlock) void k_co_sum(const SumP a) {
                 for (int d = 0; d < kCoDepth - 1; ++d) acc = add_vec<T>(acc, x[d]);
             }
         }
-        if (!act) continue;
+        if (!act || lng) continue;
         uint8_t* o = a.out + u * a.rowbytes + vb;
         if (!tail) {
             stg16_nt(o, acc);
@@ -259,29 +229,17 @@ __global__ __launch_bounds__(kCoBlock) void k_co_sum(const SumP a) {
     }
 }
 
-template <int RDW>
-__device__ inline u32x4 load_narrow(const uint8_t* p) {
-    u32x4 x = {0u, 0u, 0u, 0u};
-    if (RDW == 2) {
-        const u32x2 t = __builtin_nontemporal_load((const DML_GLOBAL u32x2_u*)p);
-        x.x = t.x; x.y = t.y;
-    } else {
-        x.x = ldg32_nt(p);
-        if (RDW == 3) { x.y = ldg32_nt(p + 4); x.z = ldg32_nt(p + 8); }
-    }
-    return x;
-}
-
 // Rows of RDW = 1, 2 or 3 dwords: one lane per unique key, kCoDepth occurrences' indices
 // and then their rows loaded before the adds.
 template <typename T, int RDW>
 __global__ __launch_bounds__(kCoBlock) void k_co_sum_narrow(const uint8_t* __restrict__ values,
                                                             const uint32_t* __restrict__ idx,
                                                             const uint32_t* __restrict__ seg, int64_t n, int64_t m,
-                                                            uint8_t* __restrict__ out) {
+                                                            uint8_t* __restrict__ out, uint32_t lmin) {
     const int64_t u = (int64_t)blockIdx.x * kCoBlock + threadIdx.x;
     if (u >= m) return;
     const uint32_t s = seg[u], e = u + 1 < m ? seg[u + 1] : (uint32_t)n;
+    if (e - s >= lmin) return;  // the long path's
     u32x4 acc = {0u, 0u, 0u, 0u};
     uint32_t k0 = s;
     for (; k0 + kCoDepth <= e; k0 += kCoDepth) {  // whole steps
@@ -307,9 +265,9 @@ void launch_sum(const SumP& a, hipStream_t st) {
     if (a.rowbytes < 16) {
         const dim3 grid((unsigned)((a.m + kCoBlock - 1) / kCoBlock)), blk(kCoBlock);
         switch ((int)(a.rowbytes / 4)) {
-            case 1: hipLaunchKernelGGL((k_co_sum_narrow<T, 1>), grid, blk, 0, st, a.values, a.idx, a.seg, a.n, a.m, a.out); break;
-            case 2: hipLaunchKernelGGL((k_co_sum_narrow<T, 2>), grid, blk, 0, st, a.values, a.idx, a.seg, a.n, a.m, a.out); break;
-            default: hipLaunchKernelGGL((k_co_sum_narrow<T, 3>), grid, blk, 0, st, a.values, a.idx, a.seg, a.n, a.m, a.out); break;
+            case 1: hipLaunchKernelGGL((k_co_sum_narrow<T, 1>), grid, blk, 0, st, a.values, a.idx, a.seg, a.n, a.m, a.out, a.lmin); break;
+            case 2: hipLaunchKernelGGL((k_co_sum_narrow<T, 2>), grid, blk, 0, st, a.values, a.idx, a.seg, a.n, a.m, a.out, a.lmin); break;
+            default: hipLaunchKernelGGL((k_co_sum_narrow<T, 3>), grid, blk, 0, st, a.values, a.idx, a.seg, a.n, a.m, a.out, a.lmin); break;
         }
         return;
     }
@@ -338,6 +296,7 @@ struct dml_coalescer {
     bool in_flight = false;
     hipEvent_t ev[6] = {};          // stage boundaries of the last call (dml_diag_coalesce_times)
     bool timed = false, timed_sum = false;
+    int64_t long_min = DML_COALESCE_LONG_MIN;  // dml_coalescer_set_long_min
 };
 
 extern "C" int dml_coalescer_create(int32_t device, dml_coalescer** out) {
@@ -436,10 +395,13 @@ extern "C" int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32
     size_t tmp = 0;
     HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const uint64_t*)nullptr, (uint64_t*)nullptr,
                                               (const uint32_t*)nullptr, (uint32_t*)nullptr, in, 0, 64, st));
-    // kin | kout | vin | vout | seg | blockoff | sort temp
+    // a segment of lmin occurrences and more takes the long path; 2^31: none does (n < 2^31)
+    const uint32_t lmin = (uint32_t)std::min<int64_t>(c->long_min, (int64_t)1 << 31);
+    const int64_t nlong = dev_values ? n / lmin : 0;  // the most long segments n occurrences hold
+    // kin | kout | vin | vout | seg | blockoff | long list | sort temp
     const size_t o_kin = 0, o_kout = o_kin + up256((size_t)n * 8), o_vin = o_kout + up256((size_t)n * 8),
                  o_vout = o_vin + up256((size_t)n * 4), o_seg = o_vout + up256((size_t)n * 4),
-                 o_boff = o_seg + up256((size_t)n * 4), o_tmp = o_boff + up256((size_t)nb * 4),
+                 o_boff = o_seg + up256((size_t)n * 4), o_list = o_boff + up256((size_t)nb * 4), o_tmp = o_list + up256((size_t)nlong * 4),
                  need = o_tmp + up256(tmp);
     if (need > c->ws_bytes) {
         if (c->ws) (void)hipFree(c->ws);
@@ -496,6 +458,22 @@ extern "C" int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32
         const int64_t nvec = std::min<int64_t>((rowbytes + 15) / 16, 64);
         a.lgG = 0;
         while (((int64_t)1 << a.lgG) < nvec) ++a.lgG;
+        a.lmin = lmin;
+        if (nlong > 0) {  // the list, then the long sums; the walks below skip what they take
+            LongP l;
+            l.values = a.values;
+            l.idx = vout;
+            l.seg = seg;
+            l.out = a.out;
+            l.n = n;
+            l.m = m;
+            l.rowbytes = rowbytes;
+            l.lmin = lmin;
+            l.list = (uint32_t*)(c->ws + o_list);
+            l.route = c->count_dev + kRouteWord;
+            co_launch_long(l, d.value_type, st);
+            HIPCHK(hipGetLastError());
+        }
         if (d.value_type == DML_ELEMENT_TYPE_FLOAT) launch_sum<float>(a, st);
         else if (d.value_type == DML_ELEMENT_TYPE_DOUBLE) launch_sum<double>(a, st);
         else launch_sum<int32_t>(a, st);
@@ -527,5 +505,25 @@ extern "C" int dml_diag_coalesce_times(dml_coalescer* c, float* ms3) {
     ms3[0] = order;
     ms3[1] = count + write;
     ms3[2] = sum;
+    return DML_OK;
+}
+
+extern "C" int dml_coalescer_set_long_min(dml_coalescer* c, int64_t v) {
+    if (!c) return set_error(DML_E_INVALID_ARG, "null coalescer");
+    if (v < 0) return set_error(DML_E_INVALID_ARG, "negative long_min");
+    c->long_min = v == 0 ? DML_COALESCE_LONG_MIN : v;
+    return DML_OK;
+}
+
+extern "C" int dml_diag_coalesce_route(dml_coalescer* c, int64_t* out2) {
+    if (!c || !out2) return set_error(DML_E_INVALID_ARG, "null coalescer or out");
+    if (!c->timed) return set_error(DML_E_INVALID_ARG, "no completed dml_coalesce_device on this context");
+    DeviceGuard g(c->device);
+    HIPCHK(hipEventSynchronize(c->done));
+    c->in_flight = false;
+    uint32_t w[2] = {0u, 0u};
+    if (c->timed_sum) HIPCHK(hipMemcpy(w, c->count_dev + kRouteWord, 8, hipMemcpyDeviceToHost));
+    out2[0] = w[0];
+    out2[1] = w[1];
     return DML_OK;
 }

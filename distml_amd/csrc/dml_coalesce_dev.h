@@ -1,0 +1,82 @@
+// dml_coalesce_dev.h — what the coalescer's two kernel files share (dml_coalesce.hip: order,
+// heads and the walk k_co_sum; dml_coalesce_long.hip: the long-segment list and its sum
+// kernels): the one add of the contract, the narrow row load, and the long
+// path's launch. Device and host; not part of the public ABI.
+#pragma once
+#include "distml_ps.h"
+#include "dml_fetch_line.h"
+#include "dml_host.h"
+
+namespace dml {
+
+constexpr int kCoBlock = 256;
+constexpr int64_t kCoSpanBytes = 1024;  // 64 lanes x 16 bytes
+
+__device__ inline uint32_t ldg32_nt(const uint8_t* p) {
+    return __builtin_nontemporal_load((const DML_GLOBAL uint32_t*)(p));
+}
+
+// One add as the reference's JVM on x86-64 makes it: rounded once (the build has
+// -ffp-contract=off), and the NaN an invalid operation creates (Inf - Inf: neither operand
+// is one) is that platform's NEGATIVE quiet NaN, 0xFFC00000 / 0xFFF8000000000000, where
+// gfx950 would create the positive one. An operand's NaN passes through, quieted, as on both.
+__device__ inline float add_ref(float a, float x) {
+    const float r = __fadd_rn(a, x);
+    return (r != r && a == a && x == x) ? __uint_as_float(0xFFC00000u) : r;
+}
+__device__ inline double add_ref(double a, double x) {
+    const double r = __dadd_rn(a, x);
+    return (r != r && a == a && x == x) ? __longlong_as_double((long long)0xFFF8000000000000ull) : r;
+}
+__device__ inline int32_t add_ref(int32_t a, int32_t x) { return (int32_t)((uint32_t)a + (uint32_t)x); }
+
+// acc + x per element of one 16-byte vector; int32 wraps.
+template <typename T> __device__ inline u32x4 add_vec(u32x4 a, u32x4 x);
+template <> __device__ inline u32x4 add_vec<float>(u32x4 a, u32x4 x) {
+    u32x4 r;
+    r.x = __float_as_uint(add_ref(__uint_as_float(a.x), __uint_as_float(x.x)));
+    r.y = __float_as_uint(add_ref(__uint_as_float(a.y), __uint_as_float(x.y)));
+    r.z = __float_as_uint(add_ref(__uint_as_float(a.z), __uint_as_float(x.z)));
+    r.w = __float_as_uint(add_ref(__uint_as_float(a.w), __uint_as_float(x.w)));
+    return r;
+}
+template <> __device__ inline u32x4 add_vec<int32_t>(u32x4 a, u32x4 x) { return a + x; }
+template <> __device__ inline u32x4 add_vec<double>(u32x4 a, u32x4 x) {
+    const double lo = add_ref(Elem<double>::from_bits(a.x, a.y), Elem<double>::from_bits(x.x, x.y));
+    const double hi = add_ref(Elem<double>::from_bits(a.z, a.w), Elem<double>::from_bits(x.z, x.w));
+    const uint64_t l = (uint64_t)__double_as_longlong(lo), h = (uint64_t)__double_as_longlong(hi);
+    u32x4 r;
+    r.x = (uint32_t)l; r.y = (uint32_t)(l >> 32); r.z = (uint32_t)h; r.w = (uint32_t)(h >> 32);
+    return r;
+}
+
+template <int RDW>
+__device__ inline u32x4 load_narrow(const uint8_t* p) {
+    u32x4 x = {0u, 0u, 0u, 0u};
+    if (RDW == 2) {
+        const u32x2 t = __builtin_nontemporal_load((const DML_GLOBAL u32x2_u*)p);
+        x.x = t.x; x.y = t.y;
+    } else {
+        x.x = ldg32_nt(p);
+        if (RDW == 3) { x.y = ldg32_nt(p + 4); x.z = ldg32_nt(p + 8); }
+    }
+    return x;
+}
+
+// The long-segment path (dml_coalesce_long.hip). `route` is two zeroed device words: the
+// number of long segments and the occurrences they hold; `list` has room for n / lmin keys.
+struct LongP {
+    const uint8_t* values;  // T[n][cols], 4-byte aligned
+    const uint32_t* idx;    // occurrence indices, sorted by key, list order inside a key
+    const uint32_t* seg;    // seg[u]: the first sorted position of unique key u
+    uint8_t* out;           // T[m][cols], 4-byte aligned
+    int64_t n, m;
+    int64_t rowbytes;
+    uint32_t lmin;          // a segment of lmin occurrences and more is long
+    uint32_t* list;         // the long keys' u, in no particular order
+    uint32_t* route;
+};
+// k_co_long_list, then k_co_sum_long or k_co_sum_long_narrow for value type `value_type`.
+void co_launch_long(const LongP& a, int32_t value_type, hipStream_t st);
+
+}  // namespace dml

@@ -635,6 +635,19 @@ class Coalescer:
         check(_lib.load().dml_diag_coalesce_times(self._h, ms))
         return tuple(ms)
 
+    def set_long_min(self, occurrences: int = 0):
+        """A key with `occurrences` occurrences and more is summed by the long-segment kernels
+        in the runs after this call; 0 restores DML_COALESCE_LONG_MIN, 2**31 and more means
+        never. The output bytes do not depend on it (dml_coalescer_set_long_min)."""
+        check(_lib.load().dml_coalescer_set_long_min(self._h, int(occurrences)))
+
+    def route(self):
+        """(long segments, occurrences they held) of the last completed run
+        (dml_diag_coalesce_route)."""
+        out = (C.c_int64 * 2)()
+        check(_lib.load().dml_diag_coalesce_route(self._h, out))
+        return tuple(out)
+
     def close(self):
         if self._h:
             self._fin()

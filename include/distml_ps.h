@@ -702,8 +702,8 @@ int dml_diag_codec_knob(int32_t knob, int64_t value);
  * the kernels that write the outputs are then enqueued on `stream` and the call returns;
  * with stream == NULL it waits for everything. Inputs must be complete in `stream` order.
  * One call is in flight per context: the next call (and dml_coalescer_destroy) first waits
- * for this one's event. The workspace (about 28 bytes per occurrence and the sort's own)
- * grows on demand and is reused. A context belongs to the device it was created for and is
+ * for this one's event. The workspace (about 28 bytes per occurrence, the sort's own and
+ * 4 bytes per possible long segment, n / long_min of them) grows on demand and is reused. A context belongs to the device it was created for and is
  * not thread-safe.
  *
  * Errors. All but DML_E_CAPACITY are found before any HIP call and before `c` is
@@ -728,11 +728,31 @@ int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32_t cols, co
 #define DML_COALESCE_BLOCK_KEYS 1024
 #define DML_COALESCE_BATCH 16
 #define DML_COALESCE_DEPTH 4
+/* Long segments. A key with DML_COALESCE_LONG_MIN occurrences and more (the default; per
+ * context, dml_coalescer_set_long_min) is summed by k_co_sum_long instead of the walk: one
+ * block per DML_COALESCE_LONG_SLICE bytes of its row fetches DML_COALESCE_LONG_TILE
+ * consecutive occurrences at a time into LDS and adds them from there, in the same order
+ * (rows under 16 bytes: one wave per key). Every output byte is the same on either path.
+ * The default is the measured crossover of one key's segment at 200 f32 columns
+ * (profiles/coalesce_long_sweep.jsonl; at cols = 1 it is 256). */
+#define DML_COALESCE_LONG_MIN 512
+#define DML_COALESCE_LONG_TILE 128
+#define DML_COALESCE_LONG_SLICE 256
+/* The threshold of `c` in occurrences, for the calls after this one. v == 0 restores
+ * DML_COALESCE_LONG_MIN; with v >= 2^31 no segment takes the long path (n < 2^31).
+ * DML_E_INVALID_ARG: null c, v < 0. The list of long keys adds 4 x n / v bytes to the
+ * workspace. */
+int dml_coalescer_set_long_min(dml_coalescer* c, int64_t v);
 /* Diagnostic / timing: HIP-event times in ms of the last completed dml_coalesce_device on
  * `c` (waits for it): ms3[0] order (pairs and sort), ms3[1] k_co_heads (count, offsets and
- * the writing pass; the host wait between them is not counted), ms3[2] the row sum (0 in
- * keys-only mode). DML_E_INVALID_ARG before the first call that ran to its end. */
+ * the writing pass; the host wait between them is not counted), ms3[2] the row sum: the
+ * long-segment list and both sum kernels (0 in keys-only mode). DML_E_INVALID_ARG before the
+ * first call that ran to its end. */
 int dml_diag_coalesce_times(dml_coalescer* c, float* ms3);
+/* Diagnostic: out2[0] the number of segments the long path summed in the last completed
+ * dml_coalesce_device on `c` (waits for it), out2[1] the occurrences they held; 0, 0 in
+ * keys-only mode. DML_E_INVALID_ARG as for dml_diag_coalesce_times. */
+int dml_diag_coalesce_route(dml_coalescer* c, int64_t* out2);
 
 /* --- native multi-GPU shard group (RCCL) -------------------------------- *
  * One process per GPU; rank r owns shard r of KeyRange.linearSplit(world)

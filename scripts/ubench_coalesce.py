@@ -11,9 +11,17 @@ Per shape every candidate is warmed up, the coalescer's output is compared betwe
 then --rounds rounds alternate the candidates; a round's figure is the median of --calls calls.
 One JSON line per shape goes to --out (default profiles/coalesce_ubench.jsonl).
 
+The sum is timed twice where the library has the threshold (dml_coalescer_set_long_min): `sum`
+with --long-min (0: the default DML_COALESCE_LONG_MIN), `sum_walk` with the threshold at never,
+so that the walk and the long-segment kernels are compared in one process; `call` is the three
+stages of the first together. --lib loads another build of the library (an older one without
+the threshold reports `sum` only), for A/B runs in alternating processes.
+
 Shapes: 200 f32 columns at n = 2^20 occurrences with (distinct) every key once, (x4) four
 occurrences per key, (zipf) a Zipf(1.1) list, (half) one key holding half the list; and
-(arr) cols = 1 at n = 2^24, four occurrences per key on average.
+(arr) cols = 1 at n = 2^24, four occurrences per key on average. The threshold sweep: (seg:L)
+200 f32 columns at n = 2^18, all distinct but one key that holds L occurrences, and (aseg:L)
+the same at cols = 1; without --long-min their threshold is L, so that segment alone is long.
 
   python scripts/ubench_coalesce.py [--shapes distinct,x4,zipf,half,arr] [--calls 5] [--rounds 3]
 """
@@ -31,7 +39,11 @@ SHAPES = ("distinct", "x4", "zipf", "half", "arr")
 
 
 def make_keys(name, rng, np):
-    n = 1 << 24 if name == "arr" else 1 << 20
+    n = 1 << 24 if name == "arr" else 1 << 18 if "seg:" in name else 1 << 20
+    if "seg:" in name:
+        k = rng.permutation(n) + 8
+        k[rng.permutation(n)[: int(name.split(":")[1])]] = 7
+        return k.astype(np.int64), (1 if name[0] == "a" else 200)
     if name == "distinct":
         k = rng.permutation(n)
     elif name == "x4":
@@ -51,13 +63,22 @@ def main():
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--long-min", type=int, default=0)
+    ap.add_argument("--lib", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "coalesce_ubench.jsonl"))
     args = ap.parse_args()
     import numpy as np
     import torch
     from distml_amd import Coalescer, DataDesc, DeviceKeys, _lib
     assert torch.cuda.is_available(), "ubench_coalesce needs the GPU"
+    if args.lib:
+        raw = C.CDLL(args.lib)
+        for sym in [s for s in _lib.SIGNATURES if not hasattr(raw, s)]:
+            del _lib.SIGNATURES[sym]
+        _lib._lib = _lib.load(args.lib)
     L = _lib.load()
+    knob = "dml_coalescer_set_long_min" in _lib.SIGNATURES
+    NEVER = 1 << 31
     lines = []
     for name in args.shapes.split(","):
         rng = np.random.default_rng(5)
@@ -79,7 +100,11 @@ def main():
         co = Coalescer(0)
         torch.cuda.synchronize()
 
-        def coalesce():
+        lm = int(name.split(":")[1]) if "seg:" in name and not args.long_min else args.long_min
+
+        def coalesce(long_min=lm):
+            if knob:
+                co.set_long_min(long_min)
             assert co.run(fmt, cols, DeviceKeys(dk.data_ptr(), n), vals.data_ptr(), kout.data_ptr(), vout.data_ptr(),
                           inv.data_ptr(), m, stream=st.cuda_stream) == m
             return co.stage_times()
@@ -104,21 +129,31 @@ def main():
         first = vout.clone()
         coalesce()
         assert torch.equal(first.view(torch.int32), vout.view(torch.int32)), name  # run to run, bit for bit
+        route = co.route() if knob else None
+        if knob:
+            coalesce(NEVER)
+            assert torch.equal(first.view(torch.int32), vout.view(torch.int32)), name  # walk and long, bit for bit
         assert torch.equal(kout.cpu(), torch.from_numpy(uk))
         del first
         inv64 = inv.long()
         acc = torch.empty((m, cols), dtype=torch.float32, device="cuda")
         copy()
         index_add()
-        per = dict(order=[], heads=[], sum=[], copy=[], index_add=[])
+        per = dict(order=[], heads=[], sum=[], call=[], copy=[], index_add=[])
+        if knob:
+            per["sum_walk"] = []
         for _ in range(args.rounds):
             t = [coalesce() for _ in range(args.calls)]
             for i, k in enumerate(("order", "heads", "sum")):
                 per[k].append(statistics.median(x[i] for x in t))
+            per["call"].append(statistics.median(sum(x) for x in t))
+            if knob:
+                per["sum_walk"].append(statistics.median(coalesce(NEVER)[2] for _ in range(args.calls)))
             per["copy"].append(statistics.median(copy() for _ in range(args.calls)))
             per["index_add"].append(statistics.median(index_add() for _ in range(args.calls)))
         best = {k: min(v) for k, v in per.items()}
         ln = dict(shape=name, n=n, m=m, cols=cols, row_bytes=row, longest_segment=int(counts.max()),
+                  long_min=lm, route=route,
                   sum_moved_bytes=moved, round_ms={k: [round(x, 4) for x in v] for k, v in per.items()},
                   best_ms={k: round(v, 4) for k, v in best.items()},
                   sum_gbs=round(moved / best["sum"] / 1e6, 1), copy_gbs=round(2 * half / best["copy"] / 1e6, 1),
