@@ -117,10 +117,13 @@ SIGNATURES = {
     "dml_record_bytes": (C.c_int, [_P(dml_desc), _i32, _u32, _P(_i64), _P(_i64)]),
     "dml_records_pack_device": (C.c_int, [_P(dml_desc), _i32, _u32, _vp, _i64, _i64, _vp, _vp, _i64, _P(_i64), _vp]),
     "dml_records_unpack_device": (C.c_int, [_P(dml_desc), _i32, _u32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "dml_records_expand_device": (C.c_int, [_P(dml_desc), _i32, _u32, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "dml_diag_codec_knob": (C.c_int, [_i32, _i64]),
     "dml_coalescer_create": (C.c_int, [_i32, _P(_vp)]),
     "dml_coalescer_destroy": (None, [_vp]),
     "dml_coalesce_device": (C.c_int, [_vp, _P(dml_desc), _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _P(_i64), _vp]),
+    "dml_coalesce_pack_device": (C.c_int, [_vp, _P(dml_desc), _i32, _u32, _vp, _i64, _vp, _vp, _i64, _vp, _vp,
+                                           _P(_i64), _P(_i64), _vp]),
     "dml_diag_coalesce_times": (C.c_int, [_vp, _P(C.c_float)]),
     "dml_coalescer_set_long_min": (C.c_int, [_vp, _i64]),
     "dml_diag_coalesce_route": (C.c_int, [_vp, _P(_i64)]),

@@ -1,6 +1,6 @@
 // dml_coalesce.hip — the device gradient coalescer (C-ABI dml_coalescer_create / _destroy,
-// dml_coalesce_device, dml_coalescer_set_long_min, dml_diag_coalesce_times / _route;
-// DESIGN.md §4.13).
+// dml_coalesce_device, dml_coalesce_pack_device, dml_coalescer_set_long_min,
+// dml_diag_coalesce_times / _route).
 //
 // The reference worker fetches through a KeyList, a HashSet<Long> (KeyList.java:14-19,59-61),
 // and accumulates its update per key in a HashMap before SparseMatrix.push writes one record
@@ -24,6 +24,9 @@
 //                 occurrence indices fetched one per lane and broadcast, kCoDepth rows' loads
 //                 issued before the first add, adds strictly in occurrence order.
 //   k_co_sum_narrow  rows under 16 bytes (arrays, 1-3 f32 / i32 columns, one f64): one lane per key
+//
+// dml_coalesce_pack_device runs the same kernels with the sum kernels in their record form
+// (REC): the sums go straight into push records, key in front, and no dense plane exists.
 //
 // A segment of the context's long_min occurrences and more is left out by both walks and
 // summed by dml_coalesce_long.hip's kernels instead: the same adds in the same order.
@@ -150,6 +153,7 @@ struct SumP {
     int64_t nspan;          // 1-KiB spans of a row
     int32_t lgG;            // log2 of the lanes of a group
     uint32_t lmin;          // a segment of lmin occurrences and more is the long path's
+    RecP rec;               // REC only: `out` is the records
 };
 
 // The sum starts at +0.0 and a sum of IEEE adds that starts there is never -0.0 (x + y is
@@ -159,7 +163,11 @@ struct SumP {
 // A row's last vector, when the row is no multiple of 16 bytes, is loaded shifted back so
 // that it ends at the row's last byte (the row is >= 16 bytes, so the load stays inside it);
 // its leading elements repeat the previous lane's sums and only the trailing dwords are stored.
-template <typename T>
+//
+// REC: the sums go to push record u's value field, and the lane that owns the row's first
+// vector stores the key in front of it (RecP, dml_coalesce_dev.h). A record's value field is
+// 4-byte aligned like a dense row, so the stores are the dense form's at another address.
+template <typename T, bool REC>
 __global__ __launch_bounds__(kCoBlock) void k_co_sum(const SumP a) {
     const int lane = threadIdx.x & 63;
     const int G = 1 << a.lgG, gl = lane & (G - 1), per = 64 >> a.lgG;
@@ -188,6 +196,10 @@ __global__ __launch_bounds__(kCoBlock) void k_co_sum(const SumP a) {
         }
         const bool lng = e - s >= a.lmin;  // the long path's: no walk and no store
         if (lng) e = s;
+        int64_t key = 0;
+        if constexpr (REC) {
+            if (live && !lng && vb == 0) key = a.rec.ukeys[u];  // in flight over the walk
+        }
         u32x4 acc = zero;
         for (uint32_t base = s; base < e; base += (uint32_t)B) {
             const int cnt = e - base < (uint32_t)B ? (int)(e - base) : B;
@@ -216,7 +228,14 @@ __global__ __launch_bounds__(kCoBlock) void k_co_sum(const SumP a) {
             }
         }
         if (!act || lng) continue;
-        uint8_t* o = a.out + u * a.rowbytes + vb;
+        uint8_t* o;
+        if constexpr (REC) {
+            uint8_t* r = a.out + u * a.rec.stride;
+            if (vb == 0) put_key(r, key, a.rec.kdw);
+            o = r + 4 * a.rec.kdw + vb;
+        } else {
+            o = a.out + u * a.rowbytes + vb;
+        }
         if (!tail) {
             stg16_nt(o, acc);
         } else {  // the trailing (rowbytes - vb) / 4 dwords of the shifted vector
@@ -231,15 +250,18 @@ __global__ __launch_bounds__(kCoBlock) void k_co_sum(const SumP a) {
 
 // Rows of RDW = 1, 2 or 3 dwords: one lane per unique key, kCoDepth occurrences' indices
 // and then their rows loaded before the adds.
-template <typename T, int RDW>
+// REC: the lane writes its whole record, key, row and pad, as ascending dwords.
+template <typename T, int RDW, bool REC>
 __global__ __launch_bounds__(kCoBlock) void k_co_sum_narrow(const uint8_t* __restrict__ values,
                                                             const uint32_t* __restrict__ idx,
                                                             const uint32_t* __restrict__ seg, int64_t n, int64_t m,
-                                                            uint8_t* __restrict__ out, uint32_t lmin) {
+                                                            uint8_t* __restrict__ out, uint32_t lmin, const RecP rec) {
     const int64_t u = (int64_t)blockIdx.x * kCoBlock + threadIdx.x;
     if (u >= m) return;
     const uint32_t s = seg[u], e = u + 1 < m ? seg[u + 1] : (uint32_t)n;
     if (e - s >= lmin) return;  // the long path's
+    int64_t key = 0;
+    if constexpr (REC) key = rec.ukeys[u];
     u32x4 acc = {0u, 0u, 0u, 0u};
     uint32_t k0 = s;
     for (; k0 + kCoDepth <= e; k0 += kCoDepth) {  // whole steps
@@ -254,26 +276,36 @@ __global__ __launch_bounds__(kCoBlock) void k_co_sum_narrow(const uint8_t* __res
     }
     for (; k0 < e; ++k0)  // the last 1 .. kCoDepth - 1 occurrences
         acc = add_vec<T>(acc, load_narrow<RDW>(values + (int64_t)idx[k0] * (RDW * 4)));
-    uint8_t* o = out + u * (RDW * 4);
+    uint8_t* o;
+    if constexpr (REC) {
+        uint8_t* r = out + u * rec.stride;
+        put_key(r, key, rec.kdw);
+        o = r + 4 * rec.kdw;
+    } else {
+        o = out + u * (RDW * 4);
+    }
     stg32_nt(o, acc.x);
     if (RDW >= 2) stg32_nt(o + 4, acc.y);
     if (RDW >= 3) stg32_nt(o + 8, acc.z);
+    if constexpr (REC) {
+        if (rec.pad) stg32_nt(o + RDW * 4, 0u);
+    }
 }
 
-template <typename T>
+template <typename T, bool REC>
 void launch_sum(const SumP& a, hipStream_t st) {
     if (a.rowbytes < 16) {
         const dim3 grid((unsigned)((a.m + kCoBlock - 1) / kCoBlock)), blk(kCoBlock);
         switch ((int)(a.rowbytes / 4)) {
-            case 1: hipLaunchKernelGGL((k_co_sum_narrow<T, 1>), grid, blk, 0, st, a.values, a.idx, a.seg, a.n, a.m, a.out, a.lmin); break;
-            case 2: hipLaunchKernelGGL((k_co_sum_narrow<T, 2>), grid, blk, 0, st, a.values, a.idx, a.seg, a.n, a.m, a.out, a.lmin); break;
-            default: hipLaunchKernelGGL((k_co_sum_narrow<T, 3>), grid, blk, 0, st, a.values, a.idx, a.seg, a.n, a.m, a.out, a.lmin); break;
+            case 1: hipLaunchKernelGGL((k_co_sum_narrow<T, 1, REC>), grid, blk, 0, st, a.values, a.idx, a.seg, a.n, a.m, a.out, a.lmin, a.rec); break;
+            case 2: hipLaunchKernelGGL((k_co_sum_narrow<T, 2, REC>), grid, blk, 0, st, a.values, a.idx, a.seg, a.n, a.m, a.out, a.lmin, a.rec); break;
+            default: hipLaunchKernelGGL((k_co_sum_narrow<T, 3, REC>), grid, blk, 0, st, a.values, a.idx, a.seg, a.n, a.m, a.out, a.lmin, a.rec); break;
         }
         return;
     }
     const int64_t per = 64 >> a.lgG, nwave = (a.m * a.nspan + per - 1) / per;
     const int64_t blocks = std::min<int64_t>((nwave + kCoBlock / 64 - 1) / (kCoBlock / 64), kCoMaxBlocks);
-    hipLaunchKernelGGL((k_co_sum<T>), dim3((unsigned)blocks), dim3(kCoBlock), 0, st, a);
+    hipLaunchKernelGGL((k_co_sum<T, REC>), dim3((unsigned)blocks), dim3(kCoBlock), 0, st, a);
 }
 
 bool overlap(const void* a, int64_t alen, const void* b, int64_t blen) {
@@ -335,6 +367,24 @@ extern "C" void dml_coalescer_destroy(dml_coalescer* c) {
     delete c;
 }
 
+namespace {
+
+// Where a call's results go: the dense form's planes, or the record form's stream.
+struct CoOut {
+    int64_t* keys_out;   // may be null in the record form: the keys then go to the workspace
+    void* values_out;    // T[m][cols], or the push records
+    int32_t* inverse;
+    int64_t cap;         // rows, or bytes of the records
+    int64_t rec_bytes;   // 0: dense; else the bytes of one push record
+    int32_t kdw, pad;
+    int64_t* out_len;    // record form: m x rec_bytes
+};
+
+int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t* dev_keys, int64_t n,
+           const void* dev_values, const CoOut& o, int64_t* out_rows, void* stream);
+
+}  // namespace
+
 extern "C" int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32_t cols, const int64_t* dev_keys,
                                    int64_t n, const void* dev_values, int64_t* dev_keys_out, void* dev_values_out,
                                    int32_t* dev_inverse_out, int64_t cap_rows, int64_t* out_rows, void* stream) {
@@ -381,8 +431,64 @@ extern "C" int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32
         *out_rows = 0;
         return DML_OK;
     }
+    const CoOut o = {dev_keys_out, dev_values_out, dev_inverse_out, cap_rows, 0, 0, 0, nullptr};
+    return co_run(c, d, rowbytes, dev_keys, n, dev_values, o, out_rows, stream);
+}
 
-    // ---- the device side
+extern "C" int dml_coalesce_pack_device(dml_coalescer* c, const dml_desc* desc, int32_t cols, uint32_t flags,
+                                        const int64_t* dev_keys, int64_t n, const void* dev_values,
+                                        void* dev_records_out, int64_t cap_bytes, int64_t* dev_keys_out,
+                                        int32_t* dev_inverse_out, int64_t* out_rows, int64_t* out_len, void* stream) {
+    // ---- argument checks, the coalescer's and the pack's: no HIP call before they pass
+    if (!c || !desc || !out_rows || !out_len)
+        return set_error(DML_E_INVALID_ARG, "null coalescer, desc, out_rows or out_len");
+    int64_t R = 0;
+    if (int rc = dml_record_bytes(desc, cols, flags, &R, nullptr)) return rc;  // desc, flags, cols, record length
+    const dml_desc d = *desc;
+    const bool matrix = d.data_type == DML_DATA_TYPE_MATRIX;
+    if (n < 0) return set_error(DML_E_INVALID_ARG, "negative occurrence count");
+    if (n > 0x7FFFFFFFll) return set_error(DML_E_UNSUPPORTED, "lists of 2^31 occurrences and more");
+    const int K = desc_key_bytes(d);
+    const int64_t rowbytes = (int64_t)desc_value_bytes(d) * (matrix ? cols : 1);
+    if (R / 4 > 0x7FFFFFFFll) return set_error(DML_E_UNSUPPORTED, "records of 2^31 dwords and more");
+    if (n > 0 && R > INT64_MAX / n) return set_error(DML_E_INVALID_ARG, "occurrence count overflows the byte length");
+    if ((((uintptr_t)dev_keys | (uintptr_t)dev_keys_out) & 7u) != 0)
+        return set_error(DML_E_INVALID_ARG, "key array is not 8-byte aligned");
+    if ((((uintptr_t)dev_values | (uintptr_t)dev_records_out | (uintptr_t)dev_inverse_out) & 3u) != 0)
+        return set_error(DML_E_INVALID_ARG, "values, records or inverse pointer is not 4-byte aligned");
+    if (n > 0 && (!dev_keys || !dev_values || !dev_records_out))
+        return set_error(DML_E_INVALID_ARG, "null keys, values or records pointer");
+    {
+        // the records never extend past min(n x R, cap_bytes) bytes, the keys past as many rows
+        const int64_t rbytes = cap_bytes < 0 ? 0 : std::min(n * R, cap_bytes);
+        const void* in[2] = {dev_keys, dev_values};
+        const int64_t inlen[2] = {n * 8, n * rowbytes};
+        const void* outp[3] = {dev_keys_out, dev_records_out, dev_inverse_out};
+        const int64_t outlen[3] = {rbytes / R * 8, rbytes, dev_inverse_out ? n * 4 : 0};
+        for (int o = 0; o < 3; ++o) {
+            for (int i = 0; i < 2; ++i)
+                if (overlap(outp[o], outlen[o], in[i], inlen[i]))
+                    return set_error(DML_E_INVALID_ARG, "coalesce output overlaps an input");
+            for (int p = o + 1; p < 3; ++p)
+                if (overlap(outp[o], outlen[o], outp[p], outlen[p]))
+                    return set_error(DML_E_INVALID_ARG, "coalesce outputs overlap");
+        }
+    }
+    if (n == 0) {
+        *out_rows = 0;
+        *out_len = 0;
+        return DML_OK;
+    }
+    const CoOut o = {dev_keys_out, dev_records_out, dev_inverse_out, cap_bytes, R, K / 4,
+                     R != K + rowbytes ? 1 : 0, out_len};
+    return co_run(c, d, rowbytes, dev_keys, n, dev_values, o, out_rows, stream);
+}
+
+namespace {
+
+// The device side of both calls, after their argument checks.
+int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t* dev_keys, int64_t n,
+           const void* dev_values, const CoOut& o, int64_t* out_rows, void* stream) {
     DeviceGuard g(c->device);
     hipStream_t st = (hipStream_t)stream;
     if (c->in_flight) {  // one call in flight per context
@@ -398,10 +504,12 @@ extern "C" int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32
     // a segment of lmin occurrences and more takes the long path; 2^31: none does (n < 2^31)
     const uint32_t lmin = (uint32_t)std::min<int64_t>(c->long_min, (int64_t)1 << 31);
     const int64_t nlong = dev_values ? n / lmin : 0;  // the most long segments n occurrences hold
-    // kin | kout | vin | vout | seg | blockoff | long list | sort temp
+    const bool rec = o.rec_bytes != 0;
+    const size_t ukeys = rec && !o.keys_out ? (size_t)n * 8 : 0;  // the record form reads the keys back
+    // kin | kout | vin | vout | seg | blockoff | long list | unique keys | sort temp
     const size_t o_kin = 0, o_kout = o_kin + up256((size_t)n * 8), o_vin = o_kout + up256((size_t)n * 8),
                  o_vout = o_vin + up256((size_t)n * 4), o_seg = o_vout + up256((size_t)n * 4),
-                 o_boff = o_seg + up256((size_t)n * 4), o_list = o_boff + up256((size_t)nb * 4), o_tmp = o_list + up256((size_t)nlong * 4),
+                 o_boff = o_seg + up256((size_t)n * 4), o_list = o_boff + up256((size_t)nb * 4), o_uk = o_list + up256((size_t)nlong * 4), o_tmp = o_uk + up256(ukeys),
                  need = o_tmp + up256(tmp);
     if (need > c->ws_bytes) {
         if (c->ws) (void)hipFree(c->ws);
@@ -438,11 +546,17 @@ extern "C" int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32
     HIPCHK(hipEventSynchronize(c->ev[2]));
     const int64_t m = (int64_t)*c->count_host;
     *out_rows = m;
-    if (m > cap_rows) return set_error(DML_E_CAPACITY, "more distinct keys than cap_rows");
+    if (rec) {
+        *o.out_len = m * o.rec_bytes;
+        if (m * o.rec_bytes > o.cap) return set_error(DML_E_CAPACITY, "coalesced push records exceed cap_bytes");
+    } else if (m > o.cap) {
+        return set_error(DML_E_CAPACITY, "more distinct keys than cap_rows");
+    }
+    int64_t* keys_out = o.keys_out ? o.keys_out : (int64_t*)(c->ws + o_uk);
 
     HIPCHK(hipEventRecord(c->ev[3], st));
     hipLaunchKernelGGL((k_co_heads<true>), dim3((unsigned)nb), blk, 0, st, (const uint64_t*)kout,
-                       (const uint32_t*)vout, n, boff, dev_keys_out, seg, dev_inverse_out);
+                       (const uint32_t*)vout, n, boff, keys_out, seg, o.inverse);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev[4], st));
     if (dev_values) {
@@ -450,7 +564,7 @@ extern "C" int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32
         a.values = (const uint8_t*)dev_values;
         a.idx = vout;
         a.seg = seg;
-        a.out = (uint8_t*)dev_values_out;
+        a.out = (uint8_t*)o.values_out;
         a.n = n;
         a.m = m;
         a.rowbytes = rowbytes;
@@ -459,6 +573,7 @@ extern "C" int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32
         a.lgG = 0;
         while (((int64_t)1 << a.lgG) < nvec) ++a.lgG;
         a.lmin = lmin;
+        a.rec = RecP{keys_out, o.rec_bytes, o.kdw, o.pad};
         if (nlong > 0) {  // the list, then the long sums; the walks below skip what they take
             LongP l;
             l.values = a.values;
@@ -471,12 +586,20 @@ extern "C" int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32
             l.lmin = lmin;
             l.list = (uint32_t*)(c->ws + o_list);
             l.route = c->count_dev + kRouteWord;
-            co_launch_long(l, d.value_type, st);
+            l.rec = a.rec;
+            co_launch_long(l, d.value_type, rec, st);
             HIPCHK(hipGetLastError());
         }
-        if (d.value_type == DML_ELEMENT_TYPE_FLOAT) launch_sum<float>(a, st);
-        else if (d.value_type == DML_ELEMENT_TYPE_DOUBLE) launch_sum<double>(a, st);
-        else launch_sum<int32_t>(a, st);
+        const int vt = d.value_type;
+        if (rec) {
+            if (vt == DML_ELEMENT_TYPE_FLOAT) launch_sum<float, true>(a, st);
+            else if (vt == DML_ELEMENT_TYPE_DOUBLE) launch_sum<double, true>(a, st);
+            else launch_sum<int32_t, true>(a, st);
+        } else {
+            if (vt == DML_ELEMENT_TYPE_FLOAT) launch_sum<float, false>(a, st);
+            else if (vt == DML_ELEMENT_TYPE_DOUBLE) launch_sum<double, false>(a, st);
+            else launch_sum<int32_t, false>(a, st);
+        }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c->ev[5], st));
         c->timed_sum = true;
@@ -491,9 +614,11 @@ extern "C" int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32
     return DML_OK;
 }
 
+}  // namespace
+
 extern "C" int dml_diag_coalesce_times(dml_coalescer* c, float* ms3) {
     if (!c || !ms3) return set_error(DML_E_INVALID_ARG, "null coalescer or ms3");
-    if (!c->timed) return set_error(DML_E_INVALID_ARG, "no completed dml_coalesce_device on this context");
+    if (!c->timed) return set_error(DML_E_INVALID_ARG, "no completed dml_coalesce_device or dml_coalesce_pack_device on this context");
     DeviceGuard g(c->device);
     HIPCHK(hipEventSynchronize(c->done));
     c->in_flight = false;
@@ -517,7 +642,7 @@ extern "C" int dml_coalescer_set_long_min(dml_coalescer* c, int64_t v) {
 
 extern "C" int dml_diag_coalesce_route(dml_coalescer* c, int64_t* out2) {
     if (!c || !out2) return set_error(DML_E_INVALID_ARG, "null coalescer or out");
-    if (!c->timed) return set_error(DML_E_INVALID_ARG, "no completed dml_coalesce_device on this context");
+    if (!c->timed) return set_error(DML_E_INVALID_ARG, "no completed dml_coalesce_device or dml_coalesce_pack_device on this context");
     DeviceGuard g(c->device);
     HIPCHK(hipEventSynchronize(c->done));
     c->in_flight = false;

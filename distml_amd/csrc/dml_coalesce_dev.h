@@ -1,7 +1,7 @@
 // dml_coalesce_dev.h — what the coalescer's two kernel files share (dml_coalesce.hip: order,
 // heads and the walk k_co_sum; dml_coalesce_long.hip: the long-segment list and its sum
-// kernels): the one add of the contract, the narrow row load, and the long
-// path's launch. Device and host; not part of the public ABI.
+// kernels): the one add of the contract, the narrow row load, the record
+// form's parameters and the long path's launch. Device and host; not part of the public ABI.
 #pragma once
 #include "distml_ps.h"
 #include "dml_fetch_line.h"
@@ -63,20 +63,42 @@ __device__ inline u32x4 load_narrow(const uint8_t* p) {
     return x;
 }
 
+// The record form of the sum kernels (dml_coalesce_pack_device; their REC instantiations):
+// `out` is then the push records' first byte and key u's sums go to record u's value field,
+// out + u x stride + 4 x kdw, behind the key that the lane (thread) storing the row's first
+// element writes just before it, and in front of a float array record's zero pad, so one
+// record, and with it one wave's records, leaves as one run of ascending stores. The dense
+// instantiations read none of this.
+struct RecP {
+    const int64_t* ukeys;  // the distinct keys, ascending (k_co_heads<true>'s keys_out)
+    int64_t stride;        // bytes of one push record
+    int32_t kdw;           // dwords of its key field: 1 or 2
+    int32_t pad;           // 1: FloatArrayStore's [f32][4 zero bytes] slot
+};
+
+// The key field of the record at `r`: the low kdw dwords of the key, little-endian (a 4-byte
+// key is the writer's (int) cast).
+__device__ inline void put_key(uint8_t* r, int64_t key, int kdw) {
+    stg32_nt(r, (uint32_t)key);
+    if (kdw == 2) stg32_nt(r + 4, (uint32_t)((uint64_t)key >> 32));
+}
+
 // The long-segment path (dml_coalesce_long.hip). `route` is two zeroed device words: the
 // number of long segments and the occurrences they hold; `list` has room for n / lmin keys.
 struct LongP {
     const uint8_t* values;  // T[n][cols], 4-byte aligned
     const uint32_t* idx;    // occurrence indices, sorted by key, list order inside a key
     const uint32_t* seg;    // seg[u]: the first sorted position of unique key u
-    uint8_t* out;           // T[m][cols], 4-byte aligned
+    uint8_t* out;           // T[m][cols], 4-byte aligned; REC: the records
     int64_t n, m;
     int64_t rowbytes;
     uint32_t lmin;          // a segment of lmin occurrences and more is long
     uint32_t* list;         // the long keys' u, in no particular order
     uint32_t* route;
+    RecP rec;               // REC only
 };
-// k_co_long_list, then k_co_sum_long or k_co_sum_long_narrow for value type `value_type`.
-void co_launch_long(const LongP& a, int32_t value_type, hipStream_t st);
+// k_co_long_list, then k_co_sum_long or k_co_sum_long_narrow for value type `value_type`;
+// `rec`: their record form.
+void co_launch_long(const LongP& a, int32_t value_type, bool rec, hipStream_t st);
 
 }  // namespace dml

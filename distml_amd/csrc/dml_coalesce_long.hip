@@ -22,6 +22,9 @@
 // add_chunk: kLongChunk adds without add_ref's NaN fix-up, which is exact unless the chunk
 // ends NaN (a NaN never leaves an accumulator); only then is the chunk redone from its saved
 // start with add_ref. The element's chain is then one add per occurrence.
+//
+// REC (dml_coalesce_pack_device): both sum kernels' owner stores go into push record u
+// (RecP, dml_coalesce_dev.h) instead of row u of a dense plane; nothing else differs.
 #include <type_traits>
 
 #include "dml_coalesce_dev.h"
@@ -69,7 +72,7 @@ __device__ inline T add_chunk(T a, const T (&x)[kLongChunk]) {
     return p;
 }
 
-template <typename T>
+template <typename T, bool REC>
 __global__ __launch_bounds__(kLongThreads) void k_co_sum_long(const LongP a, int64_t nslice) {
     __shared__ u32x4 lds[2][kLongTile * kLongVecRow];
     const int t = threadIdx.x;
@@ -81,6 +84,10 @@ __global__ __launch_bounds__(kLongThreads) void k_co_sum_long(const LongP a, int
         const int64_t soff = (item % nslice) * kLongSlice;
         const int w = (int)(a.rowbytes - soff < kLongSlice ? a.rowbytes - soff : kLongSlice);  // bytes of this slice
         const uint32_t s = a.seg[u], e = u + 1 < a.m ? a.seg[u + 1] : (uint32_t)a.n;
+        int64_t key = 0;
+        if constexpr (REC) {
+            if (t == 0 && soff == 0) key = a.rec.ukeys[u];  // in flight over the segment
+        }
         const bool col = vb < w;
         // the slice's last vector, when it is no whole one, is loaded shifted back to end at the
         // slice's last byte (the row is >= 16 bytes, so the load stays inside the row) and only
@@ -153,7 +160,14 @@ __global__ __launch_bounds__(kLongThreads) void k_co_sum_long(const LongP a, int
             __syncthreads();
         }
         if (t < nel) {
-            uint8_t* o = a.out + u * a.rowbytes + soff + (int64_t)t * sizeof(T);
+            uint8_t* o;
+            if constexpr (REC) {  // the owner of the row's first element writes the key in front of it
+                uint8_t* r = a.out + u * a.rec.stride;
+                if (t == 0 && soff == 0) put_key(r, key, a.rec.kdw);
+                o = r + 4 * a.rec.kdw + soff + (int64_t)t * sizeof(T);
+            } else {
+                o = a.out + u * a.rowbytes + soff + (int64_t)t * sizeof(T);
+            }
             if constexpr (sizeof(T) == 4) {
                 stg32_nt(o, __builtin_bit_cast(uint32_t, acc));
             } else {
@@ -178,7 +192,7 @@ __device__ inline T lane_elem(const u32x4& x, int c, int l) {
 
 // Rows of RDW = 1, 2 or 3 dwords. A slot past the segment's end holds +0.0, which leaves an
 // accumulator that started at +0.0 as it is (k_co_sum's argument).
-template <typename T, int RDW>
+template <typename T, int RDW, bool REC>
 __global__ __launch_bounds__(kCoBlock) void k_co_sum_long_narrow(const LongP a) {
     constexpr int E = RDW * 4 / (int)sizeof(T);  // elements of a row
     constexpr int NB = kLongNarrowBatch;
@@ -189,6 +203,10 @@ __global__ __launch_bounds__(kCoBlock) void k_co_sum_long_narrow(const LongP a) 
     for (uint32_t li = blockIdx.x * (kCoBlock / 64) + (threadIdx.x >> 6); li < nlong; li += gridDim.x * (kCoBlock / 64)) {
         const int64_t u = a.list[li];
         const uint32_t s = a.seg[u], e = u + 1 < a.m ? a.seg[u + 1] : (uint32_t)a.n;
+        int64_t key = 0;
+        if constexpr (REC) {
+            if (lane == 0) key = a.rec.ukeys[u];  // in flight over the segment
+        }
         uint32_t j[NB];
         u32x4 x[NB], y[NB];
         // y: the rows of the step at sorted position `b`, by j; then j: the indices of the step after it
@@ -229,7 +247,14 @@ __global__ __launch_bounds__(kCoBlock) void k_co_sum_long_narrow(const LongP a) 
             }
         }
         if (lane == 0) {
-            uint8_t* o = a.out + u * (RDW * 4);
+            uint8_t* o;
+            if constexpr (REC) {  // key, row, pad: the record's dwords in ascending order
+                uint8_t* r = a.out + u * a.rec.stride;
+                put_key(r, key, a.rec.kdw);
+                o = r + 4 * a.rec.kdw;
+            } else {
+                o = a.out + u * (RDW * 4);
+            }
 #pragma unroll
             for (int c = 0; c < E; ++c) {
                 if constexpr (sizeof(T) == 4) {
@@ -240,39 +265,48 @@ __global__ __launch_bounds__(kCoBlock) void k_co_sum_long_narrow(const LongP a) 
                     stg32_nt(o + 4, (uint32_t)(q >> 32));
                 }
             }
+            if constexpr (REC) {
+                if (a.rec.pad) stg32_nt(o + RDW * 4, 0u);
+            }
         }
     }
 }
 
-template <typename T>
+template <typename T, bool REC>
 void launch_long(const LongP& a, hipStream_t st) {
     const int64_t most = a.n / a.lmin;  // the list's capacity bounds the grid; the blocks read the count
     if (a.rowbytes >= 16) {
         const int64_t nslice = (a.rowbytes + kLongSlice - 1) / kLongSlice;
         const unsigned grid = (unsigned)std::min<int64_t>(most * nslice, kLongMaxBlocks);
-        hipLaunchKernelGGL((k_co_sum_long<T>), dim3(grid), dim3(kLongThreads), 0, st, a, nslice);
+        hipLaunchKernelGGL((k_co_sum_long<T, REC>), dim3(grid), dim3(kLongThreads), 0, st, a, nslice);
         return;
     }
     const dim3 grid((unsigned)std::min<int64_t>((most + kCoBlock / 64 - 1) / (kCoBlock / 64), kLongMaxBlocks)), blk(kCoBlock);
     if constexpr (sizeof(T) == 8) {
-        hipLaunchKernelGGL((k_co_sum_long_narrow<T, 2>), grid, blk, 0, st, a);
+        hipLaunchKernelGGL((k_co_sum_long_narrow<T, 2, REC>), grid, blk, 0, st, a);
     } else {
         switch ((int)(a.rowbytes / 4)) {
-            case 1: hipLaunchKernelGGL((k_co_sum_long_narrow<T, 1>), grid, blk, 0, st, a); break;
-            case 2: hipLaunchKernelGGL((k_co_sum_long_narrow<T, 2>), grid, blk, 0, st, a); break;
-            default: hipLaunchKernelGGL((k_co_sum_long_narrow<T, 3>), grid, blk, 0, st, a); break;
+            case 1: hipLaunchKernelGGL((k_co_sum_long_narrow<T, 1, REC>), grid, blk, 0, st, a); break;
+            case 2: hipLaunchKernelGGL((k_co_sum_long_narrow<T, 2, REC>), grid, blk, 0, st, a); break;
+            default: hipLaunchKernelGGL((k_co_sum_long_narrow<T, 3, REC>), grid, blk, 0, st, a); break;
         }
     }
 }
 
+template <bool REC>
+void launch_long_of(const LongP& a, int32_t value_type, hipStream_t st) {
+    if (value_type == DML_ELEMENT_TYPE_FLOAT) launch_long<float, REC>(a, st);
+    else if (value_type == DML_ELEMENT_TYPE_DOUBLE) launch_long<double, REC>(a, st);
+    else launch_long<int32_t, REC>(a, st);
+}
+
 }  // namespace
 
-void co_launch_long(const LongP& a, int32_t value_type, hipStream_t st) {
+void co_launch_long(const LongP& a, int32_t value_type, bool rec, hipStream_t st) {
     hipLaunchKernelGGL(k_co_long_list, dim3((unsigned)((a.m + kCoBlock - 1) / kCoBlock)), dim3(kCoBlock), 0, st, a.seg,
                        a.n, a.m, a.lmin, a.list, a.route);
-    if (value_type == DML_ELEMENT_TYPE_FLOAT) launch_long<float>(a, st);
-    else if (value_type == DML_ELEMENT_TYPE_DOUBLE) launch_long<double>(a, st);
-    else launch_long<int32_t>(a, st);
+    if (rec) launch_long_of<true>(a, value_type, st);
+    else launch_long_of<false>(a, value_type, st);
 }
 
 }  // namespace dml

@@ -105,6 +105,100 @@ __global__ __launch_bounds__(kCodecBlock) void k_rec_unpack(const UnpackP a, int
     }
 }
 
+struct ExpandP {
+    const uint32_t* rec;  // the m fetch records, as dwords
+    const int32_t* inv;   // inverse[n]: the record of output row j
+    uint8_t* line0;       // the first plane rounded down to 16 bytes; its lines are the kernel's
+    uint32_t* second;     // DUAL: the alpha plane's first dword (4-byte aligned, its own lead)
+    int64_t ndw;          // dwords of one plane (n x rowdw)
+    int64_t m;
+    int32_t rowdw;        // dwords of one row of a plane
+    int32_t recdw, kdw;
+    int32_t comp;         // STRIDE 2, one plane: which dword of a slot it takes
+    int32_t lead;
+};
+
+// The unpack's plane(s) gathered by the inverse: plane row j is the values of record inv[j].
+// Output-stationary like k_rec_unpack: one thread per 16-byte line of the first plane's
+// address. A line finds its row with one division and loads that row's inverse word once; a
+// line inside one row gathers with 16-byte loads (one at STRIDE 1, the slots' two at
+// STRIDE 2), a line over a row end dword by dword, loading the next row's inverse word as it
+// crosses. An inverse word outside [0, m) reads no record and stores nothing for its row.
+// DUAL (AdaGrad, both planes): the two loads' (value, alpha) pairs feed both planes in one
+// pass; plane dword d of the alpha plane is stored by the line that owns d of the first one,
+// as one 16-byte store at its own 4-byte alignment or as dwords at a row end. Records of a
+// key with several occurrences are re-read from L2; no LDS.
+template <int STRIDE, bool DUAL>
+__global__ __launch_bounds__(kCodecBlock) void k_rec_expand(const ExpandP a, int64_t nline) {
+    const int64_t v = (int64_t)blockIdx.x * kCodecBlock + threadIdx.x;
+    if (v >= nline) return;
+    const int64_t d0 = 4 * v - a.lead;  // plane dword of the line's first slot (< 0 only on line 0)
+    const int64_t lo = d0 < 0 ? 0 : d0;
+    const int64_t hi = d0 + 4 < a.ndw ? d0 + 4 : a.ndw;
+    if (lo >= hi) return;
+    int64_t j;
+    if (a.ndw <= 0xFFFFFFFFll) j = (int64_t)((uint32_t)lo / (uint32_t)a.rowdw);  // both fit a uint32
+    else j = lo / a.rowdw;
+    int32_t c = (int32_t)(lo - j * a.rowdw);  // dword inside row j
+    int64_t r = a.inv[j];
+    uint8_t* o = a.line0 + 16 * v;
+    if (hi - lo == 4 && c + 4 <= a.rowdw) {  // the line lies inside row j
+        if ((uint64_t)r >= (uint64_t)a.m) return;
+        const uint8_t* src = (const uint8_t*)(a.rec + r * a.recdw + a.kdw + STRIDE * c);
+        if (STRIDE == 1) {
+            stg16_nt(o, ldg16(src));
+        } else {  // slots c .. c + 3: eight dwords, all inside record r
+            const u32x4 x = ldg16(src), y = ldg16(src + 16);
+            const u32x4 val = {x.x, x.z, y.x, y.z}, alp = {x.y, x.w, y.y, y.w};
+            if (DUAL) {
+                stg16_nt(o, val);
+                stg16_nt(a.second + lo, alp);
+            } else {
+                stg16_nt(o, a.comp ? alp : val);
+            }
+        }
+        return;
+    }
+    uint32_t val[4] = {0u, 0u, 0u, 0u}, alp[4] = {0u, 0u, 0u, 0u};
+    unsigned mask = 0;  // the slots that are inside the plane and whose row has a record
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int64_t d = d0 + e;
+        if (d < lo || d >= hi) continue;
+        if (c == a.rowdw) {  // d < ndw, so row j + 1 exists
+            c = 0;
+            r = a.inv[++j];
+        }
+        if ((uint64_t)r < (uint64_t)a.m) {
+            const uint32_t* src = a.rec + r * a.recdw + a.kdw + STRIDE * c;
+            if (DUAL) {
+                const u32x2 p = ldg8(src);
+                val[e] = p.x;
+                alp[e] = p.y;
+            } else {
+                val[e] = ldg32((const uint8_t*)(src + (STRIDE == 2 ? a.comp : 0)));
+            }
+            mask |= 1u << e;
+        }
+        ++c;
+    }
+    if (mask == 0xFu) {  // a whole line: lo == d0
+        const u32x4 q = {val[0], val[1], val[2], val[3]};
+        stg16_nt(o, q);
+        if (DUAL) {
+            const u32x4 p = {alp[0], alp[1], alp[2], alp[3]};
+            stg16_nt(a.second + lo, p);
+        }
+        return;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (!(mask & (1u << e))) continue;
+        stg32_nt(o + 4 * e, val[e]);
+        if (DUAL) stg32_nt(a.second + d0 + e, alp[e]);
+    }
+}
+
 __global__ __launch_bounds__(kCodecBlock) void k_rec_keys(const uint8_t* rec, int64_t n, int64_t rec_bytes, int K,
                                                          int64_t* out) {
     const int64_t j = (int64_t)blockIdx.x * kCodecBlock + threadIdx.x;
@@ -298,6 +392,53 @@ extern "C" int dml_records_unpack_device(const dml_desc* desc, int32_t cols, uin
     if (dev_keys_out)
         hipLaunchKernelGGL(k_rec_keys, dim3((unsigned)((n + kCodecBlock - 1) / kCodecBlock)), dim3(kCodecBlock), 0, st,
                            (const uint8_t*)dev_records, n, l.fetch_rec, l.K, dev_keys_out);
+    HIPCHK(hipGetLastError());
+    if (!st) HIPCHK(hipStreamSynchronize(st));
+    return DML_OK;
+}
+
+extern "C" int dml_records_expand_device(const dml_desc* desc, int32_t cols, uint32_t flags, const void* dev_records,
+                                         int64_t m, const int32_t* dev_inverse, int64_t n, void* dev_values_out,
+                                         float* dev_alpha_out, void* stream) {
+    if (m < 0 || n < 0) return set_error(DML_E_INVALID_ARG, "negative record or row count");
+    Layout l;
+    if (int rc = layout_of(desc, cols, flags, &l)) return rc;
+    if (m > INT64_MAX / l.fetch_rec || n > INT64_MAX / ((int64_t)l.cols * 8))
+        return set_error(DML_E_INVALID_ARG, "record or row count overflows the byte length");
+    if (!dev_values_out && !dev_alpha_out) return set_error(DML_E_INVALID_ARG, "no output plane");
+    if (dev_alpha_out && !l.ada) return set_error(DML_E_INVALID_ARG, "an alpha plane, but not an AdaGrad desc");
+    if ((((uintptr_t)dev_records | (uintptr_t)dev_inverse | (uintptr_t)dev_values_out | (uintptr_t)dev_alpha_out) & 3u) != 0)
+        return set_error(DML_E_INVALID_ARG, "records, inverse or plane pointer is not 4-byte aligned");
+    if (n == 0) return DML_OK;
+    if (!dev_inverse) return set_error(DML_E_INVALID_ARG, "null inverse pointer");
+    if (m > 0 && !dev_records) return set_error(DML_E_INVALID_ARG, "null records pointer");
+    const int64_t rbytes = m * l.fetch_rec, ibytes = n * 4, vbytes = n * l.cols * l.V, abytes = n * l.cols * 4;
+    if (overlap(dev_values_out, vbytes, dev_records, rbytes) || overlap(dev_alpha_out, abytes, dev_records, rbytes) ||
+        overlap(dev_values_out, vbytes, dev_inverse, ibytes) || overlap(dev_alpha_out, abytes, dev_inverse, ibytes))
+        return set_error(DML_E_INVALID_ARG, "expand output overlaps an input");
+    if (overlap(dev_values_out, vbytes, dev_alpha_out, abytes))
+        return set_error(DML_E_INVALID_ARG, "expand output planes overlap");
+    if (m == 0) return DML_OK;  // no entry of the inverse names a record: every row stays as it is
+    const bool pair = l.ada || l.slot8, dual = dev_values_out && dev_alpha_out;
+    void* first = dev_values_out ? dev_values_out : (void*)dev_alpha_out;
+    ExpandP a;
+    a.rec = (const uint32_t*)dev_records;
+    a.inv = dev_inverse;
+    a.lead = (int32_t)(((uintptr_t)first & 15) >> 2);
+    a.line0 = (uint8_t*)first - 4 * a.lead;
+    a.second = dual ? (uint32_t*)dev_alpha_out : nullptr;
+    a.rowdw = (int32_t)((int64_t)l.cols * (pair ? 4 : l.V) / 4);
+    a.ndw = n * a.rowdw;
+    a.m = m;
+    a.recdw = (int32_t)(l.fetch_rec / 4);
+    a.kdw = l.K / 4;
+    a.comp = dev_values_out ? 0 : 1;
+    const int64_t nline = (a.ndw + a.lead + 3) / 4;
+    const dim3 grid((unsigned)((nline + kCodecBlock - 1) / kCodecBlock)), blk(kCodecBlock);
+    hipStream_t st = (hipStream_t)stream;
+    if (dual) hipLaunchKernelGGL((k_rec_expand<2, true>), grid, blk, 0, st, a, nline);
+    else if (pair) hipLaunchKernelGGL((k_rec_expand<2, false>), grid, blk, 0, st, a, nline);
+    else hipLaunchKernelGGL((k_rec_expand<1, false>), grid, blk, 0, st, a, nline);
     HIPCHK(hipGetLastError());
     if (!st) HIPCHK(hipStreamSynchronize(st));
     return DML_OK;

@@ -598,6 +598,22 @@ def unpack_fetch_device(format: DataDesc, cols: int, records_ptr: int, n: int, v
                                                 C.c_void_p(stream or None)))
 
 
+def expand_fetch_device(format: DataDesc, cols: int, records_ptr: int, m: int, inverse_ptr: int, n: int,
+                        values_ptr: Optional[int], alpha_ptr: Optional[int] = None,
+                        stream: Optional[int] = None, flags: int = 0) -> None:
+    """unpack_fetch_device gathered by a Coalescer's inverse: row j of the T[n][cols] at
+    `values_ptr` (and of AdaGrad's float[n][cols] alphas at `alpha_ptr`) is taken from the
+    fetched record `inverse[j]` of the `m` at `records_ptr`; `inverse_ptr` is the int32[n]
+    a keys-only Coalescer.run wrote. A plane whose pointer is None is skipped. An entry
+    outside [0, m) leaves its row as it was. `stream` as in unpack_fetch_device
+    (dml_records_expand_device)."""
+    check(_lib.load().dml_records_expand_device(C.byref(format.to_c()), int(cols), int(flags),
+                                                C.c_void_p(records_ptr or None), int(m),
+                                                C.c_void_p(inverse_ptr or None), int(n),
+                                                C.c_void_p(values_ptr or None), C.c_void_p(alpha_ptr or None),
+                                                C.c_void_p(stream or None)))
+
+
 # ---- the worker's KeyList + HashMap accumulate on the device (dml_coalesce_device) --------
 class Coalescer:
     """A coalescer context (dml_coalescer): workspace, a pinned count word and one event on
@@ -627,6 +643,26 @@ class Coalescer:
                                               C.c_void_p(inverse_ptr or None), int(cap_rows), C.byref(m),
                                               C.c_void_p(stream or None)))
         return m.value
+
+    def run_packed(self, format: DataDesc, cols: int, keys: DeviceKeys, values_ptr: int, out_ptr: int, cap: int,
+                   inverse_ptr: Optional[int] = None, keys_out_ptr: Optional[int] = None,
+                   stream: Optional[int] = None, flags: int = 0):
+        """run followed by pack_push_device in one call, with no dense plane between them:
+        the push records of the distinct keys of `keys`, ascending, each with the ordered sum
+        of its occurrences' rows, at `out_ptr` (4-byte aligned, `cap` bytes): the bytes
+        encode_matrix_push / encode_array_push give for the coalesced input. The inverse and
+        the distinct keys are written too where a pointer is given. Returns (m, bytes
+        written); more than `cap` raises with code DML_E_CAPACITY and nothing written.
+        `stream` and the one host wait as in run; `flags` as in pack_push_device
+        (dml_coalesce_pack_device)."""
+        m, nbytes = C.c_int64(), C.c_int64()
+        check(_lib.load().dml_coalesce_pack_device(self._h, C.byref(format.to_c()), int(cols), int(flags),
+                                                   C.c_void_p(keys.ptr or None), int(keys.n),
+                                                   C.c_void_p(values_ptr or None), C.c_void_p(out_ptr or None),
+                                                   int(cap), C.c_void_p(keys_out_ptr or None),
+                                                   C.c_void_p(inverse_ptr or None), C.byref(m), C.byref(nbytes),
+                                                   C.c_void_p(stream or None)))
+        return m.value, nbytes.value
 
     def stage_times(self):
         """(order, heads, sum) HIP-event milliseconds of the last completed run

@@ -654,8 +654,34 @@ int dml_records_pack_device(const dml_desc* desc, int32_t cols, uint32_t flags, 
 int dml_records_unpack_device(const dml_desc* desc, int32_t cols, uint32_t flags, const void* dev_records,
                               int64_t n, int64_t* dev_keys_out, void* dev_values_out, float* dev_alpha_out,
                               void* stream);
+/* dml_records_expand_device is the unpack gathered by a coalescer's inverse: the worker's
+ * step from the m records it fetched for its distinct keys to one row per occurrence.
+ * dev_values_out is T[n][cols] and row j holds the values of fetch record dev_inverse[j];
+ * dev_alpha_out is float[n][cols], row j the alphas of that record, for AdaGrad descs only
+ * (non-NULL for any other desc: DML_E_INVALID_ARG). Either plane may be NULL, not both.
+ * With both, every (value, alpha) pair of a record is read once and feeds both planes.
+ * The records are in dml_record_bytes' fetch layout (plain; AdaGrad's pairs;
+ * FloatArrayStore's [K][f32][4 pad] under either flag). The key field is not read.
+ *
+ * An inverse entry outside [0, m) reads no record and leaves its output row untouched:
+ * the row keeps the bytes it had. A wrong index therefore cannot make the kernel read out
+ * of bounds; it is not reported either, so a caller that cannot vouch for its inverse
+ * presets the planes. m == 0 with n > 0 is that case for every row: DML_OK, nothing
+ * launched.
+ *
+ * Moves, alignment, ordering and errors are dml_records_unpack_device's: dword moves only;
+ * every pointer, the inverse included, 4-byte aligned and nothing more; exactly
+ * n x cols x V bytes of each plane written (less the untouched rows), nothing read outside
+ * the m records and the n inverse words; stream == NULL waits, otherwise the kernel is
+ * enqueued and the inputs must be complete in `stream` order. DML_E_INVALID_ARG besides
+ * the unpack's cases: m < 0, n < 0, a null dev_inverse with n > 0, a null dev_records
+ * with n > 0 and m > 0, a plane that overlaps the records, the inverse or the other
+ * plane. n == 0 is DML_OK with nothing launched. */
+int dml_records_expand_device(const dml_desc* desc, int32_t cols, uint32_t flags, const void* dev_records,
+                              int64_t m, const int32_t* dev_inverse, int64_t n, void* dev_values_out,
+                              float* dev_alpha_out, void* stream);
 /* Output bytes of one wave instruction's 64 lines and of one block's tile in the codec's
- * kernels (k_rec_pack, k_rec_unpack): the sizes their tests place stream and plane ends at. */
+ * kernels (k_rec_pack, k_rec_unpack, k_rec_expand): the sizes their tests place stream and plane ends at. */
 #define DML_CODEC_WAVE_BYTES 1024
 #define DML_CODEC_BLOCK_BYTES 4096
 /* Codec knob (diagnostic / tests / timing; process-wide, read at every launch; the bytes
@@ -722,6 +748,36 @@ void dml_coalescer_destroy(dml_coalescer* c);
 int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32_t cols, const int64_t* dev_keys, int64_t n,
                         const void* dev_values, int64_t* dev_keys_out, void* dev_values_out,
                         int32_t* dev_inverse_out, int64_t cap_rows, int64_t* out_rows, void* stream);
+/* dml_coalesce_pack_device is dml_coalesce_device followed by dml_records_pack_device(desc,
+ * cols, flags, keys_out, ...) in one call, without the dense m x cols plane between them:
+ * the sum kernels store straight into push records. The bytes at dev_records_out equal what
+ * the two calls write for the same input: m records of R = dml_record_bytes' push bytes,
+ * keys ascending, each [K key LE (a 4-byte key is the low 4 bytes of the int64)][the ordered
+ * sum from +0.0][the 4 zero bytes of a float array record under
+ * DML_FLAG_FLOAT_ARRAY_REF_STRIDE]. *out_rows = m, *out_len = m x R. dev_keys_out and
+ * dev_inverse_out, each optional here, are as above. dev_values is required: keys-only mode
+ * stays with dml_coalesce_device. `flags` as for the codec.
+ *
+ * Records and values are 4-byte aligned and nothing more, key arrays 8-byte aligned. Only
+ * [dev_records_out, dev_records_out + m x R) is written, every byte of it once, so it may
+ * lie between live data. The count, the single host wait, the `stream` form, the one call in
+ * flight per context, the long-segment threshold, dml_diag_coalesce_times and
+ * dml_diag_coalesce_route are dml_coalesce_device's (the workspace holds n more keys when
+ * dev_keys_out is NULL).
+ *
+ * Errors: the union of the two calls', all but DML_E_CAPACITY before any HIP call, with
+ * *out_rows and *out_len left as they were and nothing written. DML_E_INVALID_ARG: null c /
+ * desc / out_rows / out_len, n < 0, n x R beyond int64, matrix cols <= 0, an unknown flag bit, a null dev_keys,
+ * dev_values or dev_records_out with n > 0, a misaligned pointer, an output (the records
+ * taken as min(n x R, cap_bytes) bytes, the keys as that many records' keys, the inverse as
+ * n words) that overlaps an input or another output. DML_E_BAD_DESC, DML_E_UNSUPPORTED: as
+ * above, and a record of 2^31 dwords or more. DML_E_CAPACITY: cap_bytes < m x R;
+ * *out_rows = m, *out_len = m x R, and NOTHING is written to any output, the inverse
+ * included. n == 0: DML_OK, both 0, nothing launched. */
+int dml_coalesce_pack_device(dml_coalescer* c, const dml_desc* desc, int32_t cols, uint32_t flags,
+                             const int64_t* dev_keys, int64_t n, const void* dev_values, void* dev_records_out,
+                             int64_t cap_bytes, int64_t* dev_keys_out, int32_t* dev_inverse_out, int64_t* out_rows,
+                             int64_t* out_len, void* stream);
 /* The coalescer's tiling, the sizes its tests place edges at: sorted keys per block of
  * k_co_heads; occurrence indices a group of k_co_sum fetches at a time (a group of fewer
  * lanes fetches one per lane); rows whose loads it issues before the first add. */
@@ -743,8 +799,8 @@ int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32_t cols, co
  * DML_E_INVALID_ARG: null c, v < 0. The list of long keys adds 4 x n / v bytes to the
  * workspace. */
 int dml_coalescer_set_long_min(dml_coalescer* c, int64_t v);
-/* Diagnostic / timing: HIP-event times in ms of the last completed dml_coalesce_device on
- * `c` (waits for it): ms3[0] order (pairs and sort), ms3[1] k_co_heads (count, offsets and
+/* Diagnostic / timing: HIP-event times in ms of the last completed dml_coalesce_device or
+ * dml_coalesce_pack_device on `c` (waits for it): ms3[0] order (pairs and sort), ms3[1] k_co_heads (count, offsets and
  * the writing pass; the host wait between them is not counted), ms3[2] the row sum: the
  * long-segment list and both sum kernels (0 in keys-only mode). DML_E_INVALID_ARG before the
  * first call that ran to its end. */

@@ -23,6 +23,16 @@ occurrences per key, (zipf) a Zipf(1.1) list, (half) one key holding half the li
 200 f32 columns at n = 2^18, all distinct but one key that holds L occurrences, and (aseg:L)
 the same at cols = 1; without --long-min their threshold is L, so that segment alone is long.
 
+--packed times dml_coalesce_pack_device's sum stage (`fused`, where the loaded library has the
+call) beside the two calls it replaces on the same inputs: dml_coalesce_device's `sum` stage
+and k_rec_pack (`pack`, HIP events around dml_records_pack_device). Run it once on this build
+and once with --lib (and --label parent) on the parent's, in alternating processes: the parent's `sum` + `pack` is
+the yardstick of `fused`, and the two builds' `sum` show whether the dense form moved.
+--expand times dml_records_expand_device at 200 f32 columns and AdaGrad 200 (both planes),
+n = 2^20, over the distinct, x4 and zipf lists, beside the plain copy of its
+m x F + n x row bytes and k_rec_unpack plus torch's gather. Both write to
+profiles/coalesce_pack_ubench.jsonl unless --out says otherwise (appending).
+
   python scripts/ubench_coalesce.py [--shapes distinct,x4,zipf,half,arr] [--calls 5] [--rounds 3]
 """
 import argparse
@@ -58,6 +68,139 @@ def make_keys(name, rng, np):
     return k.astype(np.int64), (1 if name == "arr" else 200)
 
 
+def timed(st, fn):
+    """Milliseconds of what fn enqueues on stream st, by HIP events."""
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(st)
+    fn()
+    e1.record(st)
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def rounds_of(cands, rounds, calls):
+    """{name: [per round, the median of `calls` calls]} with the candidates alternating."""
+    per = {k: [] for k in cands}
+    for fn in cands.values():
+        fn()
+    names = list(cands)
+    for r in range(rounds):  # each round starts one candidate later: none always follows the same one
+        for k in names[r % len(names):] + names[:r % len(names)]:
+            per[k].append(statistics.median(cands[k]() for _ in range(calls)))
+    return per
+
+
+def emit(ln, per, out):
+    ln["round_ms"] = {k: [round(x, 4) for x in v] for k, v in per.items()}
+    ln["best_ms"] = {k: round(min(v), 4) for k, v in per.items()}
+    print(json.dumps(ln), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "a") as f:
+        f.write(json.dumps(ln) + "\n")
+
+
+def bench_packed(args, np, torch):
+    from distml_amd import Coalescer, DataDesc, DeviceKeys, _lib, pack_push_device, record_bytes
+    fused = "dml_coalesce_pack_device" in _lib.SIGNATURES
+    for name in args.shapes.split(","):
+        keys, cols = make_keys(name, np.random.default_rng(5), np)
+        n, m = len(keys), len(np.unique(keys))
+        fmt = DataDesc(1 if cols > 1 else 0, 1, 1, False, True, False)
+        R = record_bytes(fmt, cols)[0]
+        dk = torch.from_numpy(keys).cuda()
+        vals = torch.randn((n, cols), dtype=torch.float32, device="cuda")
+        kout = torch.empty(m, dtype=torch.int64, device="cuda")
+        vout = torch.empty((m, cols), dtype=torch.float32, device="cuda")
+        rec2 = torch.empty(m * R // 4, dtype=torch.int32, device="cuda")
+        rec1 = torch.empty(m * R // 4, dtype=torch.int32, device="cuda")
+        st = torch.cuda.Stream()
+        co = Coalescer(0)
+        if args.long_min:
+            co.set_long_min(args.long_min)
+        torch.cuda.synchronize()
+
+        def dense():
+            co.run(fmt, cols, DeviceKeys(dk.data_ptr(), n), vals.data_ptr(), kout.data_ptr(), vout.data_ptr(), None, m,
+                   stream=st.cuda_stream)
+            return co.stage_times()[2]
+
+        def pack():
+            return timed(st, lambda: pack_push_device(fmt, cols, DeviceKeys(kout.data_ptr(), m), vout.data_ptr(), m,
+                                                      rec2.data_ptr(), m * R, stream=st.cuda_stream))
+
+        def packed():
+            co.run_packed(fmt, cols, DeviceKeys(dk.data_ptr(), n), vals.data_ptr(), rec1.data_ptr(), m * R,
+                          stream=st.cuda_stream)
+            return co.stage_times()[2]
+
+        cands = dict(sum=dense, pack=pack)
+        if fused:
+            cands["fused"] = packed
+        per = rounds_of(cands, args.rounds, args.calls)
+        if fused:
+            torch.cuda.synchronize()
+            assert torch.equal(rec1, rec2), name  # the fused bytes are the two calls'
+        emit(dict(mode="packed", lib=args.label, shape=name, n=n, m=m, cols=cols, record_bytes=R,
+                  two_call_bytes=(n + m) * 4 * cols + m * (4 * cols + R), fused_bytes=n * 4 * cols + m * R), per, args.out)
+        co.close()
+        del dk, vals, kout, vout, rec1, rec2
+        torch.cuda.empty_cache()
+
+
+def bench_expand(args, np, torch):
+    from distml_amd import DataDesc, _lib, expand_fetch_device, record_bytes, unpack_fetch_device
+    L = _lib.load()
+    for ada in (False, True):
+        for name in ("distinct", "x4", "zipf"):
+            keys, cols = make_keys(name, np.random.default_rng(5), np)
+            uk, hinv = np.unique(keys, return_inverse=True)
+            n, m = len(keys), len(uk)
+            fmt = DataDesc(1, 1, 1, False, True, ada)
+            F = record_bytes(fmt, cols)[1]
+            planes = 2 if ada else 1
+            moved = m * F + planes * n * 4 * cols
+            rec = torch.randint(0, 1 << 31, (m * F // 4,), dtype=torch.int32, device="cuda")
+            inv = torch.from_numpy(hinv.reshape(-1).astype(np.int32)).cuda()
+            inv64 = inv.long()
+            occ = [torch.empty((n, cols), dtype=torch.float32, device="cuda") for _ in range(planes)]
+            uni = [torch.empty((m, cols), dtype=torch.float32, device="cuda") for _ in range(planes)]
+            half = (moved // 2 + 15) & ~15
+            src = torch.empty(half, dtype=torch.uint8, device="cuda").fill_(1)
+            dst = torch.empty(half, dtype=torch.uint8, device="cuda")
+            st = torch.cuda.Stream()
+            torch.cuda.synchronize()
+
+            def expand():
+                return timed(st, lambda: expand_fetch_device(fmt, cols, rec.data_ptr(), m, inv.data_ptr(), n,
+                                                             occ[0].data_ptr(), occ[1].data_ptr() if ada else None,
+                                                             stream=st.cuda_stream))
+
+            def copy():
+                ms = C.c_float()
+                assert L.dml_diag_stream(1, dst.data_ptr(), src.data_ptr(), half, C.c_void_p(st.cuda_stream),
+                                         C.byref(ms)) == 0
+                return ms.value
+
+            def unpack_gather():
+                def go():
+                    unpack_fetch_device(fmt, cols, rec.data_ptr(), m, uni[0].data_ptr(),
+                                        uni[1].data_ptr() if ada else None, None, stream=st.cuda_stream)
+                    with torch.cuda.stream(st):
+                        for u, o in zip(uni, occ2):
+                            torch.index_select(u, 0, inv64, out=o)
+                return timed(st, go)
+
+            occ2 = [torch.empty_like(o) for o in occ]
+            per = rounds_of(dict(expand=expand, copy=copy, unpack_gather=unpack_gather), args.rounds, args.calls)
+            torch.cuda.synchronize()
+            assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(occ, occ2)), name
+            ln = dict(mode="expand", shape=name, ada=ada, n=n, m=m, cols=cols, fetch_record_bytes=F, moved_bytes=moved)
+            emit(ln, per, args.out)
+            del rec, inv, inv64, occ, occ2, uni, src, dst
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default=",".join(SHAPES))
@@ -65,8 +208,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--long-min", type=int, default=0)
     ap.add_argument("--lib", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "coalesce_ubench.jsonl"))
+    ap.add_argument("--label", default="this", help="the `lib` field of --packed's lines")
+    ap.add_argument("--packed", action="store_true")
+    ap.add_argument("--expand", action="store_true")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "coalesce_pack_ubench.jsonl" if args.packed or args.expand
+                                        else "coalesce_ubench.jsonl")
     import numpy as np
     import torch
     from distml_amd import Coalescer, DataDesc, DeviceKeys, _lib
@@ -76,6 +224,9 @@ def main():
         for sym in [s for s in _lib.SIGNATURES if not hasattr(raw, s)]:
             del _lib.SIGNATURES[sym]
         _lib._lib = _lib.load(args.lib)
+    if args.packed or args.expand:
+        (bench_packed if args.packed else bench_expand)(args, np, torch)
+        return
     L = _lib.load()
     knob = "dml_coalescer_set_long_min" in _lib.SIGNATURES
     NEVER = 1 << 31
