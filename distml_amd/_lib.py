@@ -124,6 +124,8 @@ SIGNATURES = {
     "dml_coalesce_device": (C.c_int, [_vp, _P(dml_desc), _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _P(_i64), _vp]),
     "dml_coalesce_pack_device": (C.c_int, [_vp, _P(dml_desc), _i32, _u32, _vp, _i64, _vp, _vp, _i64, _vp, _vp,
                                            _P(_i64), _P(_i64), _vp]),
+    "dml_coalesce_elems_device": (C.c_int, [_vp, _P(dml_desc), _i32, _u32, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64,
+                                            _vp, _vp, _P(_i64), _P(_i64), _vp]),
     "dml_diag_coalesce_times": (C.c_int, [_vp, _P(C.c_float)]),
     "dml_coalescer_set_long_min": (C.c_int, [_vp, _i64]),
     "dml_diag_coalesce_route": (C.c_int, [_vp, _P(_i64)]),
@@ -199,6 +201,12 @@ DML_COALESCE_DEPTH = 4
 DML_COALESCE_LONG_MIN = 512
 DML_COALESCE_LONG_TILE = 128
 DML_COALESCE_LONG_SLICE = 256
+# ... and element updates (dml_coalesce_elems_device): the output forms, the most elements
+# per occurrence, and the dwords of a row that one k_co_elems item holds in LDS
+DML_ELEMS_ROWS = 0
+DML_ELEMS_RECORDS = 1
+DML_COALESCE_ELEMS_MAX_PER_OCC = 16
+DML_COALESCE_ELEMS_SLICE = 1024
 
 
 class NativeLibraryMissing(RuntimeError):

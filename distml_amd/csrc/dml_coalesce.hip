@@ -1,5 +1,5 @@
 // dml_coalesce.hip — the device gradient coalescer (C-ABI dml_coalescer_create / _destroy,
-// dml_coalesce_device, dml_coalesce_pack_device, dml_coalescer_set_long_min,
+// dml_coalesce_device, dml_coalesce_pack_device, dml_coalesce_elems_device, dml_coalescer_set_long_min,
 // dml_diag_coalesce_times / _route).
 //
 // The reference worker fetches through a KeyList, a HashSet<Long> (KeyList.java:14-19,59-61),
@@ -377,11 +377,18 @@ struct CoOut {
     int64_t cap;         // rows, or bytes of the records
     int64_t rec_bytes;   // 0: dense; else the bytes of one push record
     int32_t kdw, pad;
-    int64_t* out_len;    // record form: m x rec_bytes
+    int64_t* out_len;    // record form: m x rec_bytes; dense form, when given: m x rowbytes
+};
+
+// The third sum mode's input (dml_coalesce_elems_device): element updates instead of rows.
+struct CoElems {
+    const int32_t* cols;  // int32[n][per]
+    const int32_t* vals;  // int32[n][per]
+    int32_t ncols, per;
 };
 
 int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t* dev_keys, int64_t n,
-           const void* dev_values, const CoOut& o, int64_t* out_rows, void* stream);
+           const void* dev_values, const CoElems* el, const CoOut& o, int64_t* out_rows, void* stream);
 
 }  // namespace
 
@@ -432,7 +439,7 @@ extern "C" int dml_coalesce_device(dml_coalescer* c, const dml_desc* desc, int32
         return DML_OK;
     }
     const CoOut o = {dev_keys_out, dev_values_out, dev_inverse_out, cap_rows, 0, 0, 0, nullptr};
-    return co_run(c, d, rowbytes, dev_keys, n, dev_values, o, out_rows, stream);
+    return co_run(c, d, rowbytes, dev_keys, n, dev_values, nullptr, o, out_rows, stream);
 }
 
 extern "C" int dml_coalesce_pack_device(dml_coalescer* c, const dml_desc* desc, int32_t cols, uint32_t flags,
@@ -481,14 +488,77 @@ extern "C" int dml_coalesce_pack_device(dml_coalescer* c, const dml_desc* desc, 
     }
     const CoOut o = {dev_keys_out, dev_records_out, dev_inverse_out, cap_bytes, R, K / 4,
                      R != K + rowbytes ? 1 : 0, out_len};
-    return co_run(c, d, rowbytes, dev_keys, n, dev_values, o, out_rows, stream);
+    return co_run(c, d, rowbytes, dev_keys, n, dev_values, nullptr, o, out_rows, stream);
+}
+
+extern "C" int dml_coalesce_elems_device(dml_coalescer* c, const dml_desc* desc, int32_t cols, uint32_t flags,
+                                         const int64_t* dev_keys, int64_t n, int32_t per_occ, const int32_t* dev_cols,
+                                         const int32_t* dev_vals, int32_t form, void* dev_out, int64_t cap_bytes,
+                                         int64_t* dev_keys_out, int32_t* dev_inverse_out, int64_t* out_rows,
+                                         int64_t* out_len, void* stream) {
+    // ---- argument checks, the pack call's and the elements': no HIP call before they pass
+    if (!c || !desc || !out_rows || !out_len)
+        return set_error(DML_E_INVALID_ARG, "null coalescer, desc, out_rows or out_len");
+    int64_t R = 0;
+    if (int rc = dml_record_bytes(desc, cols, flags, &R, nullptr)) return rc;  // desc, flags, cols, record length
+    const dml_desc d = *desc;
+    if (d.data_type != DML_DATA_TYPE_MATRIX)
+        return set_error(DML_E_UNSUPPORTED, "an array's element update is dml_coalesce_device with cols = 1");
+    if (d.value_type != DML_ELEMENT_TYPE_INT || d.ada_grad)
+        return set_error(DML_E_UNSUPPORTED, "element updates are int32 only: float sums depend on their order");
+    if (form != DML_ELEMS_ROWS && form != DML_ELEMS_RECORDS) return set_error(DML_E_INVALID_ARG, "unknown output form");
+    if (per_occ < 1 || per_occ > DML_COALESCE_ELEMS_MAX_PER_OCC)
+        return set_error(DML_E_INVALID_ARG, "per_occ outside 1 .. DML_COALESCE_ELEMS_MAX_PER_OCC");
+    if (n < 0) return set_error(DML_E_INVALID_ARG, "negative occurrence count");
+    if (n > 0x7FFFFFFFll) return set_error(DML_E_UNSUPPORTED, "lists of 2^31 occurrences and more");
+    const bool rec = form == DML_ELEMS_RECORDS;
+    const int K = desc_key_bytes(d);
+    const int64_t rowbytes = 4 * (int64_t)cols;
+    const int64_t ob = rec ? R : rowbytes;  // bytes of one output row or record
+    if (ob / 4 > 0x7FFFFFFFll) return set_error(DML_E_UNSUPPORTED, "rows or records of 2^31 dwords and more");
+    if (n > 0 && ob > INT64_MAX / n) return set_error(DML_E_INVALID_ARG, "occurrence count overflows the byte length");
+    if ((((uintptr_t)dev_keys | (uintptr_t)dev_keys_out) & 7u) != 0)
+        return set_error(DML_E_INVALID_ARG, "key array is not 8-byte aligned");
+    if ((((uintptr_t)dev_cols | (uintptr_t)dev_vals | (uintptr_t)dev_out | (uintptr_t)dev_inverse_out) & 3u) != 0)
+        return set_error(DML_E_INVALID_ARG, "columns, values, output or inverse pointer is not 4-byte aligned");
+    if (n > 0 && (!dev_keys || !dev_cols || !dev_vals || !dev_out))
+        return set_error(DML_E_INVALID_ARG, "null keys, columns, values or output pointer");
+    if (n > 0 && !rec && !dev_keys_out) return set_error(DML_E_INVALID_ARG, "the row form needs dev_keys_out");
+    {
+        // the output never extends past min(n x ob, cap_bytes) bytes, the keys past as many rows
+        const int64_t obytes = cap_bytes < 0 ? 0 : std::min(n * ob, cap_bytes);
+        const void* in[3] = {dev_keys, dev_cols, dev_vals};
+        const int64_t inlen[3] = {n * 8, n * per_occ * 4, n * per_occ * 4};
+        const void* outp[3] = {dev_keys_out, dev_out, dev_inverse_out};
+        const int64_t outlen[3] = {obytes / ob * 8, obytes, dev_inverse_out ? n * 4 : 0};
+        for (int o = 0; o < 3; ++o) {
+            for (int i = 0; i < 3; ++i)
+                if (overlap(outp[o], outlen[o], in[i], inlen[i]))
+                    return set_error(DML_E_INVALID_ARG, "coalesce output overlaps an input");
+            for (int p = o + 1; p < 3; ++p)
+                if (overlap(outp[o], outlen[o], outp[p], outlen[p]))
+                    return set_error(DML_E_INVALID_ARG, "coalesce outputs overlap");
+        }
+    }
+    if (n == 0) {
+        *out_rows = 0;
+        *out_len = 0;
+        return DML_OK;
+    }
+    const CoElems el = {dev_cols, dev_vals, cols, per_occ};
+    // the dense form's capacity in rows: m > cap_bytes / rowbytes exactly when m x rowbytes > cap_bytes
+    const CoOut o = rec ? CoOut{dev_keys_out, dev_out, dev_inverse_out, cap_bytes, R, K / 4, 0, out_len}
+                        : CoOut{dev_keys_out, dev_out, dev_inverse_out, cap_bytes < 0 ? -1 : cap_bytes / rowbytes, 0, 0, 0, out_len};
+    return co_run(c, d, rowbytes, dev_keys, n, nullptr, &el, o, out_rows, stream);
 }
 
 namespace {
 
-// The device side of both calls, after their argument checks.
+// The device side of the three calls, after their argument checks. The sum is dense or
+// record (`o`) over rows (`dev_values`) or over element updates (`el`; then `rowbytes` is the
+// output row's).
 int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t* dev_keys, int64_t n,
-           const void* dev_values, const CoOut& o, int64_t* out_rows, void* stream) {
+           const void* dev_values, const CoElems* el, const CoOut& o, int64_t* out_rows, void* stream) {
     DeviceGuard g(c->device);
     hipStream_t st = (hipStream_t)stream;
     if (c->in_flight) {  // one call in flight per context
@@ -503,7 +573,7 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
                                               (const uint32_t*)nullptr, (uint32_t*)nullptr, in, 0, 64, st));
     // a segment of lmin occurrences and more takes the long path; 2^31: none does (n < 2^31)
     const uint32_t lmin = (uint32_t)std::min<int64_t>(c->long_min, (int64_t)1 << 31);
-    const int64_t nlong = dev_values ? n / lmin : 0;  // the most long segments n occurrences hold
+    const int64_t nlong = dev_values || el ? n / lmin : 0;  // the most long segments n occurrences hold
     const bool rec = o.rec_bytes != 0;
     const size_t ukeys = rec && !o.keys_out ? (size_t)n * 8 : 0;  // the record form reads the keys back
     // kin | kout | vin | vout | seg | blockoff | long list | unique keys | sort temp
@@ -549,8 +619,9 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
     if (rec) {
         *o.out_len = m * o.rec_bytes;
         if (m * o.rec_bytes > o.cap) return set_error(DML_E_CAPACITY, "coalesced push records exceed cap_bytes");
-    } else if (m > o.cap) {
-        return set_error(DML_E_CAPACITY, "more distinct keys than cap_rows");
+    } else {
+        if (o.out_len) *o.out_len = m * rowbytes;
+        if (m > o.cap) return set_error(DML_E_CAPACITY, "more distinct keys than cap_rows");
     }
     int64_t* keys_out = o.keys_out ? o.keys_out : (int64_t*)(c->ws + o_uk);
 
@@ -559,7 +630,28 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
                        (const uint32_t*)vout, n, boff, keys_out, seg, o.inverse);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev[4], st));
-    if (dev_values) {
+    if (el) {
+        ElemsP a;
+        a.cols = el->cols;
+        a.vals = el->vals;
+        a.idx = vout;
+        a.seg = seg;
+        a.out = (uint8_t*)o.values_out;
+        a.n = n;
+        a.m = m;
+        a.rowbytes = rowbytes;
+        a.nslice = co_elems_slices(el->ncols);
+        a.ncols = el->ncols;
+        a.per = el->per;
+        a.lmin = lmin;
+        a.list = (uint32_t*)(c->ws + o_list);
+        a.route = c->count_dev + kRouteWord;
+        a.rec = RecP{keys_out, o.rec_bytes, o.kdw, o.pad};
+        co_launch_elems(a, rec, nlong > 0, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->ev[5], st));
+        c->timed_sum = true;
+    } else if (dev_values) {
         SumP a;
         a.values = (const uint8_t*)dev_values;
         a.idx = vout;

@@ -1,7 +1,8 @@
-// dml_coalesce_dev.h — what the coalescer's two kernel files share (dml_coalesce.hip: order,
+// dml_coalesce_dev.h — what the coalescer's kernel files share (dml_coalesce.hip: order,
 // heads and the walk k_co_sum; dml_coalesce_long.hip: the long-segment list and its sum
-// kernels): the one add of the contract, the narrow row load, the record
-// form's parameters and the long path's launch. Device and host; not part of the public ABI.
+// kernels; dml_coalesce_elems.hip: the element-update sum): the one add
+// of the contract, the narrow row load, the record form's parameters and the long path's and
+// the element sum's launches. Device and host; not part of the public ABI.
 #pragma once
 #include "distml_ps.h"
 #include "dml_fetch_line.h"
@@ -100,5 +101,30 @@ struct LongP {
 // k_co_long_list, then k_co_sum_long or k_co_sum_long_narrow for value type `value_type`;
 // `rec`: their record form.
 void co_launch_long(const LongP& a, int32_t value_type, bool rec, hipStream_t st);
+// k_co_long_list alone: the keys u of [0, m) with lmin occurrences and more, and the route words.
+void co_launch_long_list(const uint32_t* seg, int64_t n, int64_t m, uint32_t lmin, uint32_t* list, uint32_t* route,
+                         hipStream_t st);
+
+// The element-update sum (dml_coalesce_elems.hip; dml_coalesce_elems_device): occurrence j
+// holds `per` (column, delta) pairs, and row / record u of `out` is the dense int32 row of
+// key u's elements. `list` and `route` as in LongP.
+struct ElemsP {
+    const int32_t* cols;  // int32[n][per], 4-byte aligned
+    const int32_t* vals;  // int32[n][per], 4-byte aligned
+    const uint32_t* idx;  // occurrence indices, sorted by key
+    const uint32_t* seg;  // seg[u]: the first sorted position of unique key u
+    uint8_t* out;         // int32[m][ncols], 4-byte aligned; REC: the records
+    int64_t n, m;
+    int64_t rowbytes;     // 4 x ncols
+    int64_t nslice;       // co_elems_slices(ncols)
+    int32_t ncols, per;
+    uint32_t lmin;        // a segment of lmin occurrences and more is long
+    uint32_t* list;
+    uint32_t* route;
+    RecP rec;             // REC only
+};
+int64_t co_elems_slices(int32_t ncols);
+// has_long: k_co_long_list and k_co_elems_long first; then k_co_elems. `rec`: their record form.
+void co_launch_elems(const ElemsP& a, bool rec, bool has_long, hipStream_t st);
 
 }  // namespace dml

@@ -302,9 +302,14 @@ void launch_long_of(const LongP& a, int32_t value_type, hipStream_t st) {
 
 }  // namespace
 
+void co_launch_long_list(const uint32_t* seg, int64_t n, int64_t m, uint32_t lmin, uint32_t* list, uint32_t* route,
+                         hipStream_t st) {
+    hipLaunchKernelGGL(k_co_long_list, dim3((unsigned)((m + kCoBlock - 1) / kCoBlock)), dim3(kCoBlock), 0, st, seg, n, m,
+                       lmin, list, route);
+}
+
 void co_launch_long(const LongP& a, int32_t value_type, bool rec, hipStream_t st) {
-    hipLaunchKernelGGL(k_co_long_list, dim3((unsigned)((a.m + kCoBlock - 1) / kCoBlock)), dim3(kCoBlock), 0, st, a.seg,
-                       a.n, a.m, a.lmin, a.list, a.route);
+    co_launch_long_list(a.seg, a.n, a.m, a.lmin, a.list, a.route, st);
     if (rec) launch_long_of<true>(a, value_type, st);
     else launch_long_of<false>(a, value_type, st);
 }

@@ -664,6 +664,31 @@ class Coalescer:
                                                    C.c_void_p(stream or None)))
         return m.value, nbytes.value
 
+    def run_elems(self, format: DataDesc, cols: int, keys: DeviceKeys, cols_ptr: int, vals_ptr: int, per_occ: int,
+                  out_ptr: int, cap: int, records: bool = False, keys_out_ptr: Optional[int] = None,
+                  inverse_ptr: Optional[int] = None, stream: Optional[int] = None, flags: int = 0):
+        """Element updates to one dense int32 row per key, a LightLDA worker's push
+        (LightLDA.scala:224-239): occurrence j of `keys` holds `per_occ` (column, delta) pairs,
+        the int32[keys.n][per_occ] at `cols_ptr` and `vals_ptr` (a token's move is per_occ = 2:
+        (old, -1), (new, +1)). Row u at `out_ptr` (4-byte aligned, `cap` bytes) is the sum mod
+        2**32 per column of the deltas of the distinct key u, keys ascending; `records`: the
+        rows as push records, the bytes encode_matrix_push gives, instead of an
+        int32[m][cols] plane. A column outside [0, cols) adds nothing; its key is still
+        listed. The distinct keys (required for the plane) and the inverse are written where
+        a pointer is given. Returns (m, bytes written); more than `cap` raises with code
+        DML_E_CAPACITY and nothing written. int32 dense-column matrix formats only. `stream`
+        and the one host wait as in run; `flags` as in pack_push_device
+        (dml_coalesce_elems_device)."""
+        m, nbytes = C.c_int64(), C.c_int64()
+        check(_lib.load().dml_coalesce_elems_device(self._h, C.byref(format.to_c()), int(cols), int(flags),
+                                                    C.c_void_p(keys.ptr or None), int(keys.n), int(per_occ),
+                                                    C.c_void_p(cols_ptr or None), C.c_void_p(vals_ptr or None),
+                                                    _lib.DML_ELEMS_RECORDS if records else _lib.DML_ELEMS_ROWS,
+                                                    C.c_void_p(out_ptr or None), int(cap),
+                                                    C.c_void_p(keys_out_ptr or None), C.c_void_p(inverse_ptr or None),
+                                                    C.byref(m), C.byref(nbytes), C.c_void_p(stream or None)))
+        return m.value, nbytes.value
+
     def stage_times(self):
         """(order, heads, sum) HIP-event milliseconds of the last completed run
         (dml_diag_coalesce_times)."""

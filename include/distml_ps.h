@@ -778,6 +778,65 @@ int dml_coalesce_pack_device(dml_coalescer* c, const dml_desc* desc, int32_t col
                              const int64_t* dev_keys, int64_t n, const void* dev_values, void* dev_records_out,
                              int64_t cap_bytes, int64_t* dev_keys_out, int32_t* dev_inverse_out, int64_t* out_rows,
                              int64_t* out_len, void* stream);
+/* dml_coalesce_elems_device coalesces ELEMENT updates. A LightLDA worker moves a token of a
+ * word from an old topic to a new one and pushes, per distinct word, the dense int32 row
+ * new - old through a KeyList of the words (LightLDA.scala:171-184,224-239). A sampler on the
+ * device holds the moves: n occurrences (tokens), each a key and per_occ (column, delta)
+ * pairs; a move is per_occ = 2, (old, -1) and (new, +1). The call turns them into one dense
+ * int32 row per distinct key without a one-hot row per token ever existing.
+ *
+ * Inputs: dev_keys int64[n]; dev_cols and dev_vals int32[n][per_occ], row-major,
+ * 1 <= per_occ <= DML_COALESCE_ELEMS_MAX_PER_OCC. The n keys are sorted, not the
+ * n x per_occ elements.
+ * Result: the distinct keys ascending as signed 64-bit values (*out_rows = m) and the inverse,
+ * exactly as dml_coalesce_device writes them, and row u with
+ *   out[u][c] = sum of dev_vals[j][e] mod 2^32 over every (j, e) with dev_keys[j] == key u
+ *   and dev_cols[j][e] == c;
+ * a column nothing lists holds 0. The adds wrap and are not checked (the store's push checks
+ * negativity); they commute, so the result is exactly defined on either route and the kernels
+ * accumulate a row in LDS with LDS atomics. An element whose column is outside [0, cols) adds
+ * nothing and is not reported; its key is still listed (the KeyList holds the word whatever
+ * the sampler did), and it cannot make a kernel read or write out of bounds.
+ * form DML_ELEMS_ROWS: dev_out is int32[m][cols], *out_len = m x cols x 4; dev_keys_out is
+ * required. form DML_ELEMS_RECORDS: dev_out is m push records, the bytes
+ * dml_records_pack_device(desc, cols, flags, keys_out, ...) writes for that row plane: [K key
+ * LE (a 4-byte key is the low dword)][cols x int32 LE], *out_len = m x R; dev_keys_out is
+ * optional, as in dml_coalesce_pack_device. dev_inverse_out is optional in both.
+ *
+ * Descs: matrix descs with value_type int32 and dense_column. f32, f64 and AdaGrad descs are
+ * DML_E_UNSUPPORTED: their sums depend on the order, the project pins order, and no reference
+ * worker produces float element updates. Array descs are DML_E_UNSUPPORTED: an array's
+ * element update already is dml_coalesce_device with cols = 1.
+ *
+ * A row is cut into slices of DML_COALESCE_ELEMS_SLICE dwords; one wave (k_co_elems), or for
+ * a key with long_min occurrences and more one block (k_co_elems_long), owns a slice in LDS
+ * for the whole segment. Every output byte is the same on either route.
+ *
+ * Alignment, the bytes written ([dev_out, dev_out + *out_len), m x 8 key bytes, n x 4 inverse
+ * bytes), the one host wait, `stream`, one call in flight per context,
+ * dml_coalescer_set_long_min, dml_diag_coalesce_times and dml_diag_coalesce_route are
+ * dml_coalesce_pack_device's.
+ *
+ * Errors, all but DML_E_CAPACITY before any HIP call and before `c` is dereferenced, with
+ * *out_rows and *out_len left as they were. DML_E_INVALID_ARG: null c / desc / out_rows /
+ * out_len, n < 0, cols <= 0, per_occ outside 1..16, an unknown form or flag bit, a null
+ * dev_keys, dev_cols, dev_vals or dev_out with n > 0, a null dev_keys_out in the row form, a
+ * misaligned pointer, an output (taken as min(n x row or R, cap_bytes) bytes, the keys as that
+ * many rows' keys, the inverse as n words) that overlaps one of the three inputs or another
+ * output. DML_E_BAD_DESC, DML_E_UNSUPPORTED: as above, a sparse-column desc, n >= 2^31, a row
+ * or record of 2^31 dwords. DML_E_CAPACITY: cap_bytes < m x row or R; *out_rows = m and
+ * *out_len say what was needed and NOTHING is written, the inverse included. n == 0: DML_OK,
+ * both 0, nothing launched. */
+#define DML_ELEMS_ROWS    0   /* dev_out: int32[m][cols]            */
+#define DML_ELEMS_RECORDS 1   /* dev_out: m push records [K key LE][cols x int32 LE] */
+#define DML_COALESCE_ELEMS_MAX_PER_OCC 16
+#define DML_COALESCE_ELEMS_SLICE 1024 /* dwords of one row slice held in LDS */
+int dml_coalesce_elems_device(dml_coalescer* c, const dml_desc* desc, int32_t cols, uint32_t flags,
+                              const int64_t* dev_keys, int64_t n, int32_t per_occ,
+                              const int32_t* dev_cols, const int32_t* dev_vals,
+                              int32_t form, void* dev_out, int64_t cap_bytes,
+                              int64_t* dev_keys_out, int32_t* dev_inverse_out,
+                              int64_t* out_rows, int64_t* out_len, void* stream);
 /* The coalescer's tiling, the sizes its tests place edges at: sorted keys per block of
  * k_co_heads; occurrence indices a group of k_co_sum fetches at a time (a group of fewer
  * lanes fetches one per lane); rows whose loads it issues before the first add. */

@@ -32,6 +32,7 @@ the yardstick of `fused`, and the two builds' `sum` show whether the dense form 
 n = 2^20, over the distinct, x4 and zipf lists, beside the plain copy of its
 m x F + n x row bytes and k_rec_unpack plus torch's gather. Both write to
 profiles/coalesce_pack_ubench.jsonl unless --out says otherwise (appending).
+--elems times dml_coalesce_elems_device (see bench_elems) into profiles/coalesce_elems_ubench.jsonl.
 
   python scripts/ubench_coalesce.py [--shapes distinct,x4,zipf,half,arr] [--calls 5] [--rounds 3]
 """
@@ -46,6 +47,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SHAPES = ("distinct", "x4", "zipf", "half", "arr")
+ELEMS_SHAPES = ("uniform", "zipf", "half", "narrow", "seg:128", "seg:256", "seg:512", "seg:1024", "seg:4096")
 
 
 def make_keys(name, rng, np):
@@ -201,6 +203,101 @@ def bench_expand(args, np, torch):
             torch.cuda.empty_cache()
 
 
+def bench_elems(args, np, torch):
+    """dml_coalesce_elems_device, record form, per_occ = 2 (a LightLDA move).
+    Shapes: uniform / zipf / half at 1 000 columns and narrow at 64, n = 2^20 tokens; seg:L, one
+    key of L tokens among 2^18 distinct ones. `sum` is the call's sum stage at --long-min (seg:L:
+    at L), `sum_short` with the threshold at never, `call` its three stages, `order` the sort's;
+    `copy` the plain copy of the n x per_occ x 8 + m x R bytes the stage must move; `index_put`
+    today's route on the same inputs (zeroed plane, index_put_(accumulate=True) with the inverse
+    given, pack_push_device); `onehot` run_packed's sum stage fed one one-hot-pair row per token."""
+    from distml_amd import Coalescer, DataDesc, DeviceKeys, _lib, pack_push_device, record_bytes
+    L, per_occ, NEVER = _lib.load(), 2, 1 << 31
+    for name in args.shapes.split(","):
+        rng = np.random.default_rng(5)
+        if "seg:" in name:
+            keys, cols = make_keys(name, rng, np)[0], 1000
+        else:
+            n = 1 << 20
+            cols = 64 if name == "narrow" else 1000
+            keys = (np.minimum(rng.zipf(1.1, size=n), 1 << 20) if name == "zipf" else rng.integers(0, 65536, size=n)).astype(np.int64)
+            if name == "half":
+                keys[rng.permutation(n)[: n // 2]] = 7
+        n = len(keys)
+        uk, hinv = np.unique(keys, return_inverse=True)
+        m = len(uk)
+        fmt = DataDesc(1, 0, 0, False, True, False)
+        R = record_bytes(fmt, cols)[0]
+        moved = n * per_occ * 8 + m * R
+        dk = torch.from_numpy(keys).cuda()
+        dc = torch.from_numpy(rng.integers(0, cols, size=(n, per_occ)).astype(np.int32)).cuda()
+        dv = torch.tensor([-1, 1], dtype=torch.int32, device="cuda").repeat(n, 1).contiguous()
+        rec1 = torch.empty(m * R // 4, dtype=torch.int32, device="cuda")
+        rec2 = torch.empty_like(rec1)
+        plane = torch.empty((m, cols), dtype=torch.int32, device="cuda")
+        ukd = torch.from_numpy(uk).cuda()
+        rows64 = torch.from_numpy(hinv.reshape(-1)).cuda().long()[:, None].expand(n, per_occ)
+        cols64 = dc.long()
+        half = (moved // 2 + 15) & ~15
+        src = torch.empty(half, dtype=torch.uint8, device="cuda").fill_(1)
+        dst = torch.empty(half, dtype=torch.uint8, device="cuda")
+        st = torch.cuda.Stream()
+        co = Coalescer(0)
+        lm = int(name.split(":")[1]) if "seg:" in name and not args.long_min else args.long_min
+        torch.cuda.synchronize()
+
+        def elems(long_min=lm, out=rec1):
+            co.set_long_min(long_min)
+            assert co.run_elems(fmt, cols, DeviceKeys(dk.data_ptr(), n), dc.data_ptr(), dv.data_ptr(), per_occ,
+                                out.data_ptr(), m * R, records=True, stream=st.cuda_stream) == (m, m * R)
+            return co.stage_times()
+
+        def copy():
+            ms = C.c_float()
+            assert L.dml_diag_stream(1, dst.data_ptr(), src.data_ptr(), half, C.c_void_p(st.cuda_stream), C.byref(ms)) == 0
+            return ms.value
+
+        def index_put():
+            def go():
+                with torch.cuda.stream(st):
+                    plane.zero_()
+                    plane.index_put_((rows64, cols64), dv, accumulate=True)
+                pack_push_device(fmt, cols, DeviceKeys(ukd.data_ptr(), m), plane.data_ptr(), m, rec2.data_ptr(), m * R,
+                                 stream=st.cuda_stream)
+            return timed(st, go)
+
+        cands = dict(sum=lambda: elems()[2], sum_short=lambda: elems(NEVER)[2], call=lambda: sum(elems()),
+                     order=lambda: elems()[0], copy=copy, index_put=index_put)
+        hot = None
+        if "seg:" not in name:  # the n x cols one-hot plane: 4 GiB at 1 000 columns
+            hot = torch.zeros((n, cols), dtype=torch.int32, device="cuda")
+            hot.index_put_((torch.arange(n, device="cuda")[:, None].expand(n, per_occ), cols64), dv, accumulate=True)
+
+            def onehot():
+                co.set_long_min(0)
+                co.run_packed(fmt, cols, DeviceKeys(dk.data_ptr(), n), hot.data_ptr(), rec2.data_ptr(), m * R,
+                              stream=st.cuda_stream)
+                return co.stage_times()[2]
+            cands["onehot"] = onehot
+        elems()
+        route = co.route()
+        index_put()
+        torch.cuda.synchronize()
+        assert torch.equal(rec1, rec2), name  # today's route writes the same bytes
+        elems(NEVER, rec2)
+        torch.cuda.synchronize()
+        assert torch.equal(rec1, rec2), name  # and so does the short route
+        per = rounds_of(cands, args.rounds, args.calls)
+        best = {k: min(v) for k, v in per.items()}
+        emit(dict(mode="elems", shape=name, n=n, m=m, cols=cols, per_occ=per_occ, record_bytes=R, long_min=lm, route=route,
+                  longest_segment=int(np.bincount(hinv.reshape(-1)).max()), sum_moved_bytes=moved,
+                  sum_over_copy=round(best["sum"] / best["copy"], 3), index_put_over_sum=round(best["index_put"] / best["sum"], 3)),
+             per, args.out)
+        co.close()
+        del dk, dc, dv, rec1, rec2, plane, rows64, cols64, src, dst, hot
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default=",".join(SHAPES))
@@ -211,10 +308,13 @@ def main():
     ap.add_argument("--label", default="this", help="the `lib` field of --packed's lines")
     ap.add_argument("--packed", action="store_true")
     ap.add_argument("--expand", action="store_true")
+    ap.add_argument("--elems", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "coalesce_pack_ubench.jsonl" if args.packed or args.expand
-                                        else "coalesce_ubench.jsonl")
+    args.out = args.out or os.path.join(ROOT, "profiles", "coalesce_elems_ubench.jsonl" if args.elems else
+                                        "coalesce_pack_ubench.jsonl" if args.packed or args.expand else "coalesce_ubench.jsonl")
+    if args.elems and args.shapes == ",".join(SHAPES):
+        args.shapes = ",".join(ELEMS_SHAPES)
     import numpy as np
     import torch
     from distml_amd import Coalescer, DataDesc, DeviceKeys, _lib
@@ -224,8 +324,8 @@ def main():
         for sym in [s for s in _lib.SIGNATURES if not hasattr(raw, s)]:
             del _lib.SIGNATURES[sym]
         _lib._lib = _lib.load(args.lib)
-    if args.packed or args.expand:
-        (bench_packed if args.packed else bench_expand)(args, np, torch)
+    if args.packed or args.expand or args.elems:
+        (bench_elems if args.elems else bench_packed if args.packed else bench_expand)(args, np, torch)
         return
     L = _lib.load()
     knob = "dml_coalescer_set_long_min" in _lib.SIGNATURES
