@@ -129,6 +129,8 @@ SIGNATURES = {
     "dml_diag_coalesce_times": (C.c_int, [_vp, _P(C.c_float)]),
     "dml_coalescer_set_long_min": (C.c_int, [_vp, _i64]),
     "dml_diag_coalesce_route": (C.c_int, [_vp, _P(_i64)]),
+    "dml_coalescer_set_key_range": (C.c_int, [_vp, _i64, _i64]),
+    "dml_diag_coalesce_order": (C.c_int, [_vp, _P(_i32)]),
     "dml_group_unique_id": (C.c_int, [_vp, _i32]),
     "dml_group_push_exchange": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
     "dml_group_push_moments": (C.c_int, [_vp, _P(_vp), _P(_i64), _i32]),
@@ -201,6 +203,12 @@ DML_COALESCE_DEPTH = 4
 DML_COALESCE_LONG_MIN = 512
 DML_COALESCE_LONG_TILE = 128
 DML_COALESCE_LONG_SLICE = 256
+# ... the bounded order stage (dml_coalescer_set_key_range): digit bits, words of a tile, the most
+# blocks of a pass, the most passes
+DML_COALESCE_ORDER_BITS = 8
+DML_COALESCE_ORDER_TILE = 2048
+DML_COALESCE_ORDER_MAX_BLOCKS = 512
+DML_COALESCE_ORDER_MAX_PASSES = 3
 # ... and element updates (dml_coalesce_elems_device): the output forms, the most elements
 # per occurrence, and the dwords of a row that one k_co_elems item holds in LDS
 DML_ELEMS_ROWS = 0

@@ -1,6 +1,6 @@
 // dml_coalesce.hip — the device gradient coalescer (C-ABI dml_coalescer_create / _destroy,
 // dml_coalesce_device, dml_coalesce_pack_device, dml_coalesce_elems_device, dml_coalescer_set_long_min,
-// dml_diag_coalesce_times / _route).
+// dml_coalescer_set_key_range, dml_diag_coalesce_times / _route / _order).
 //
 // The reference worker fetches through a KeyList, a HashSet<Long> (KeyList.java:14-19,59-61),
 // and accumulates its update per key in a HashMap before SparseMatrix.push writes one record
@@ -11,7 +11,9 @@
 // reference store holds after one handlePush of the occurrences (FloatMatrixStore.java:200-222).
 //
 //   k_co_pairs    (key ^ sign bit, occurrence index) pairs; hipcub's stable radix sort orders
-//                 them, so the indices of one key stay in list order
+//                 them, so the indices of one key stay in list order. With a key range
+//                 declared (dml_coalescer_set_key_range) dml_coalesce_order.hip's passes leave
+//                 the same two arrays instead, and these two run only if a key was outside it
 //   k_co_heads    over the sorted keys, kCoBlockKeys per block: head flag key[i] != key[i-1],
 //                 a block scan. <false> leaves the block's head count; k_co_offsets turns the
 //                 counts into carried block offsets and the total, which the host reads;
@@ -329,6 +331,9 @@ struct dml_coalescer {
     hipEvent_t ev[6] = {};          // stage boundaries of the last call (dml_diag_coalesce_times)
     bool timed = false, timed_sum = false;
     int64_t long_min = DML_COALESCE_LONG_MIN;  // dml_coalescer_set_long_min
+    uint64_t kr_first = 0, kr_span = 0;  // dml_coalescer_set_key_range; span 0: none declared
+    uint32_t epoch = 0;                  // what the bounded order stage's range check stores to count_dev[1]
+    int32_t order[3] = {0, 0, 0};        // dml_diag_coalesce_order
 };
 
 extern "C" int dml_coalescer_create(int32_t device, dml_coalescer** out) {
@@ -341,6 +346,7 @@ extern "C" int dml_coalescer_create(int32_t device, dml_coalescer** out) {
     dml_coalescer* c = new dml_coalescer;
     c->device = device;
     hipError_t e = hipMalloc((void**)&c->count_dev, 256);
+    if (e == hipSuccess) e = hipMemset(c->count_dev, 0, 256);  // the flag word differs from every epoch
     if (e == hipSuccess) e = hipHostMalloc((void**)&c->count_host, 64, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done, hipEventDisableTiming);
     for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipEventCreate(&c->ev[i]);
@@ -579,8 +585,12 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
     // kin | kout | vin | vout | seg | blockoff | long list | unique keys | sort temp
     const size_t o_kin = 0, o_kout = o_kin + up256((size_t)n * 8), o_vin = o_kout + up256((size_t)n * 8),
                  o_vout = o_vin + up256((size_t)n * 4), o_seg = o_vout + up256((size_t)n * 4),
-                 o_boff = o_seg + up256((size_t)n * 4), o_list = o_boff + up256((size_t)nb * 4), o_uk = o_list + up256((size_t)nlong * 4), o_tmp = o_uk + up256(ukeys),
-                 need = o_tmp + up256(tmp);
+                 o_boff = o_seg + up256((size_t)n * 4), o_list = o_boff + up256((size_t)nb * 4), o_uk = o_list + up256((size_t)nlong * 4), o_tmp = o_uk + up256(ukeys);
+    // A declared key range: the bounded order stage (dml_coalesce_order.hip). Its second word
+    // buffer and its counts lie where the library sort's temporaries do; its first is kin.
+    const bool bounded = c->kr_span != 0 && co_order_passes(c->kr_span) <= DML_COALESCE_ORDER_MAX_PASSES;
+    const size_t o_cnt = o_tmp + up256((size_t)n * 8);
+    const size_t need = std::max(o_tmp + up256(tmp), bounded ? o_cnt + up256(co_order_count_bytes()) : 0);
     if (need > c->ws_bytes) {
         if (c->ws) (void)hipFree(c->ws);
         c->ws = nullptr;
@@ -600,20 +610,40 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
     uint32_t* boff = (uint32_t*)(c->ws + o_boff);
     const dim3 blk(kCoBlock);
 
-    HIPCHK(hipEventRecord(c->ev[0], st));
-    hipLaunchKernelGGL(k_co_pairs, dim3((unsigned)((n + kCoBlock - 1) / kCoBlock)), blk, 0, st, dev_keys, n, kin, vin);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(c->ws + o_tmp, tmp, (const uint64_t*)kin, kout, (const uint32_t*)vin,
-                                              vout, in, 0, 64, st));
-    HIPCHK(hipEventRecord(c->ev[1], st));
-    hipLaunchKernelGGL((k_co_heads<false>), dim3((unsigned)nb), blk, 0, st, (const uint64_t*)kout,
-                       (const uint32_t*)vout, n, boff, (int64_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr);
-    hipLaunchKernelGGL(k_co_offsets, dim3(1), blk, 0, st, boff, nb, c->count_dev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->count_host, c->count_dev, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(c->ev[2], st));
-    // the one host wait: nothing is written to an output before the count is known to fit
-    HIPCHK(hipEventSynchronize(c->ev[2]));
+    c->order[0] = c->order[1] = c->order[2] = 0;
+    if (bounded && ++c->epoch == 0) c->epoch = 1;
+    for (int attempt = 0;; ++attempt) {
+        const bool own = bounded && attempt == 0;
+        HIPCHK(hipEventRecord(c->ev[0], st));
+        if (own) {
+            const OrderP op = {dev_keys, n, c->kr_first, c->kr_span, kin, (uint64_t*)(c->ws + o_tmp),
+                               (uint32_t*)(c->ws + o_cnt), kout, vout, c->count_dev + 1, c->epoch};
+            co_launch_order(op, st);
+            HIPCHK(hipGetLastError());
+        } else {
+            hipLaunchKernelGGL(k_co_pairs, dim3((unsigned)((n + kCoBlock - 1) / kCoBlock)), blk, 0, st, dev_keys, n, kin, vin);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipcub::DeviceRadixSort::SortPairs(c->ws + o_tmp, tmp, (const uint64_t*)kin, kout, (const uint32_t*)vin,
+                                                      vout, in, 0, 64, st));
+        }
+        HIPCHK(hipEventRecord(c->ev[1], st));
+        hipLaunchKernelGGL((k_co_heads<false>), dim3((unsigned)nb), blk, 0, st, (const uint64_t*)kout,
+                           (const uint32_t*)vout, n, boff, (int64_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr);
+        hipLaunchKernelGGL(k_co_offsets, dim3(1), blk, 0, st, boff, nb, c->count_dev);
+        HIPCHK(hipGetLastError());
+        // the count and, beside it, the range check's flag word
+        HIPCHK(hipMemcpyAsync(c->count_host, c->count_dev, own ? 8 : 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipEventRecord(c->ev[2], st));
+        // the one host wait: nothing is written to an output before the count is known to fit
+        HIPCHK(hipEventSynchronize(c->ev[2]));
+        if (!own) break;
+        if (c->count_host[1] != c->epoch) {  // every key was inside the declared range
+            c->order[0] = 1;
+            c->order[1] = co_order_passes(c->kr_span);
+            break;
+        }
+        c->order[2] = 1;  // a key outside it: the library sort orders the list, and a second wait
+    }
     const int64_t m = (int64_t)*c->count_host;
     *out_rows = m;
     if (rec) {
@@ -729,6 +759,26 @@ extern "C" int dml_coalescer_set_long_min(dml_coalescer* c, int64_t v) {
     if (!c) return set_error(DML_E_INVALID_ARG, "null coalescer");
     if (v < 0) return set_error(DML_E_INVALID_ARG, "negative long_min");
     c->long_min = v == 0 ? DML_COALESCE_LONG_MIN : v;
+    return DML_OK;
+}
+
+extern "C" int dml_coalescer_set_key_range(dml_coalescer* c, int64_t first, int64_t last) {
+    if (!c) return set_error(DML_E_INVALID_ARG, "null coalescer");
+    if (first > last) return set_error(DML_E_INVALID_ARG, "key range with first > last");
+    const uint64_t span = (uint64_t)last - (uint64_t)first;
+    if (span > (1ull << 32)) return set_error(DML_E_UNSUPPORTED, "key ranges of more than 2^32 keys");
+    c->kr_first = span ? (uint64_t)first : 0;  // first == last: no declaration
+    c->kr_span = span;
+    return DML_OK;
+}
+
+extern "C" int dml_diag_coalesce_order(dml_coalescer* c, int32_t* out3) {
+    if (!c || !out3) return set_error(DML_E_INVALID_ARG, "null coalescer or out");
+    if (!c->timed) return set_error(DML_E_INVALID_ARG, "no completed dml_coalesce_device or dml_coalesce_pack_device on this context");
+    DeviceGuard g(c->device);
+    HIPCHK(hipEventSynchronize(c->done));
+    c->in_flight = false;
+    for (int i = 0; i < 3; ++i) out3[i] = c->order[i];
     return DML_OK;
 }
 

@@ -1,6 +1,7 @@
 // dml_coalesce_dev.h — what the coalescer's kernel files share (dml_coalesce.hip: order,
 // heads and the walk k_co_sum; dml_coalesce_long.hip: the long-segment list and its sum
-// kernels; dml_coalesce_elems.hip: the element-update sum): the one add
+// kernels; dml_coalesce_elems.hip: the element-update sum; dml_coalesce_order.hip: the order
+// stage for keys in a declared range): the one add
 // of the contract, the narrow row load, the record form's parameters and the long path's and
 // the element sum's launches. Device and host; not part of the public ABI.
 #pragma once
@@ -126,5 +127,27 @@ struct ElemsP {
 int64_t co_elems_slices(int32_t ncols);
 // has_long: k_co_long_list and k_co_elems_long first; then k_co_elems. `rec`: their record form.
 void co_launch_elems(const ElemsP& a, bool rec, bool has_long, hipStream_t st);
+
+// The order stage for keys declared to lie in [first, first + span), 1 <= span <= 2^32
+// (dml_coalesce_order.hip; dml_coalescer_set_key_range): kout[i] = key ^ sign bit and
+// vout[i] = occurrence index, by key and then by list position, what the library sort leaves.
+// `a` and `b` hold n words each and `count` co_order_count_bytes(); none of them is kout or
+// vout. A key outside the range makes some thread store `epoch` to *flag; kout and vout are
+// then not the order (every access stays in bounds).
+struct OrderP {
+    const int64_t* keys;
+    int64_t n;
+    uint64_t first, span;
+    uint64_t* a;
+    uint64_t* b;
+    uint32_t* count;
+    uint64_t* kout;
+    uint32_t* vout;
+    uint32_t* flag;
+    uint32_t epoch;
+};
+int co_order_passes(uint64_t span);
+size_t co_order_count_bytes();
+void co_launch_order(const OrderP& o, hipStream_t st);
 
 }  // namespace dml

@@ -702,6 +702,22 @@ class Coalescer:
         never. The output bytes do not depend on it (dml_coalescer_set_long_min)."""
         check(_lib.load().dml_coalescer_set_long_min(self._h, int(occurrences)))
 
+    def set_key_range(self, first: int, last: int):
+        """Declares that the keys of the runs after this call lie in [first, last): they are
+        then ordered by the library's own radix sort over the bits of that span, not by the
+        generic 64-bit sort. A verified hint: a key outside the range costs a second order
+        stage and changes no output byte. first == last clears it; more than 2**32 keys raise
+        with code DML_E_UNSUPPORTED (dml_coalescer_set_key_range)."""
+        check(_lib.load().dml_coalescer_set_key_range(self._h, int(first), int(last)))
+
+    def order_route(self):
+        """(1 if the bounded stage ordered the last completed run else 0, its radix passes,
+        1 if a key outside the declared range sent the run back to the library sort)
+        (dml_diag_coalesce_order)."""
+        out = (C.c_int32 * 3)()
+        check(_lib.load().dml_diag_coalesce_order(self._h, out))
+        return tuple(out)
+
     def route(self):
         """(long segments, occurrences they held) of the last completed run
         (dml_diag_coalesce_route)."""

@@ -864,6 +864,37 @@ int dml_coalescer_set_long_min(dml_coalescer* c, int64_t v);
  * long-segment list and both sum kernels (0 in keys-only mode). DML_E_INVALID_ARG before the
  * first call that ran to its end. */
 int dml_diag_coalesce_times(dml_coalescer* c, float* ms3);
+/* A declared key range: an opt-in, hand-written order stage.
+ * dml_coalescer_set_key_range declares that the keys of the calls after it on `c` lie in
+ * [first, last). The three calls then order their list with a stable radix sort of this
+ * library's own over the bits of last - first - 1 alone, in
+ * ceil(bits / DML_COALESCE_ORDER_BITS) passes over 8-byte words, instead of the library sort's
+ * eight passes over 64-bit keys. The declaration is a hint that is verified and can never
+ * change an output byte: the first pass checks every key, the verdict reaches the host with
+ * the count at the call's one wait, and if a key was outside the range the list is ordered
+ * again by the library sort before anything is written (one more wait). No kernel reads or
+ * writes out of bounds whatever the keys are. The library sort also orders the list when no
+ * range is declared (the default: the calls are exactly what they were) and when the range
+ * needs more than DML_COALESCE_ORDER_MAX_PASSES passes. The workspace then holds
+ * 256 x DML_COALESCE_ORDER_MAX_BLOCKS more counters.
+ * first == last clears the declaration. A plain field update: no HIP call, and it does not
+ * wait for a call in flight, whose order stage is already enqueued.
+ * DML_E_INVALID_ARG: null c, first > last. DML_E_UNSUPPORTED: last - first > 2^32; the
+ * context is unchanged. */
+int dml_coalescer_set_key_range(dml_coalescer* c, int64_t first, int64_t last);
+/* The bounded order stage's tiling: bits of a digit at most; words of a tile (a block's unit:
+ * four waves, a contiguous quarter each, 64 words a round); the most blocks of a pass (a
+ * longer list gives every block a run of several tiles); the most passes it is chosen for. */
+#define DML_COALESCE_ORDER_BITS 8
+#define DML_COALESCE_ORDER_TILE 2048
+#define DML_COALESCE_ORDER_MAX_BLOCKS 512
+#define DML_COALESCE_ORDER_MAX_PASSES 3 /* measured: profiles/coalesce_order_ubench.jsonl */
+/* Diagnostic: how the last completed call on `c` (waits for it) ordered its list. out3[0]: 0
+ * the library sort, 1 the bounded stage; out3[1]: the radix passes it ran (0 for the library
+ * sort); out3[2]: 1 if a key outside the declared range was met and the order was redone by
+ * the library sort (then out3[0] and out3[1] are 0). DML_E_INVALID_ARG as for
+ * dml_diag_coalesce_times. */
+int dml_diag_coalesce_order(dml_coalescer* c, int32_t out3[3]);
 /* Diagnostic: out2[0] the number of segments the long path summed in the last completed
  * dml_coalesce_device on `c` (waits for it), out2[1] the occurrences they held; 0, 0 in
  * keys-only mode. DML_E_INVALID_ARG as for dml_diag_coalesce_times. */

@@ -33,6 +33,12 @@ n = 2^20, over the distinct, x4 and zipf lists, beside the plain copy of its
 m x F + n x row bytes and k_rec_unpack plus torch's gather. Both write to
 profiles/coalesce_pack_ubench.jsonl unless --out says otherwise (appending).
 --elems times dml_coalesce_elems_device (see bench_elems) into profiles/coalesce_elems_ubench.jsonl.
+--key-range FIRST:LAST (or `auto`: the list's smallest key to its largest) declares the range
+(dml_coalescer_set_key_range), so that `order` is the bounded stage's time; the
+line then holds the route (dml_diag_coalesce_order) and, for context only, `torch_sort`:
+torch.sort(stable=True) of the int32 relative keys. Its yardstick is `order` of the parent's
+library (--lib, --label parent) in alternating processes, every process with --append and
+--out profiles/coalesce_order_ubench.jsonl.
 
   python scripts/ubench_coalesce.py [--shapes distinct,x4,zipf,half,arr] [--calls 5] [--rounds 3]
 """
@@ -244,6 +250,10 @@ def bench_elems(args, np, torch):
         st = torch.cuda.Stream()
         co = Coalescer(0)
         lm = int(name.split(":")[1]) if "seg:" in name and not args.long_min else args.long_min
+        kr = None
+        if args.key_range:
+            kr = (int(keys.min()), int(keys.max()) + 1) if args.key_range == "auto" else tuple(map(int, args.key_range.split(":")))
+            co.set_key_range(*kr)
         torch.cuda.synchronize()
 
         def elems(long_min=lm, out=rec1):
@@ -289,7 +299,7 @@ def bench_elems(args, np, torch):
         assert torch.equal(rec1, rec2), name  # and so does the short route
         per = rounds_of(cands, args.rounds, args.calls)
         best = {k: min(v) for k, v in per.items()}
-        emit(dict(mode="elems", shape=name, n=n, m=m, cols=cols, per_occ=per_occ, record_bytes=R, long_min=lm, route=route,
+        emit(dict(mode="elems", lib=args.label, key_range=kr, order_route=co.order_route() if kr else None, shape=name, n=n, m=m, cols=cols, per_occ=per_occ, record_bytes=R, long_min=lm, route=route,
                   longest_segment=int(np.bincount(hinv.reshape(-1)).max()), sum_moved_bytes=moved,
                   sum_over_copy=round(best["sum"] / best["copy"], 3), index_put_over_sum=round(best["index_put"] / best["sum"], 3)),
              per, args.out)
@@ -309,6 +319,8 @@ def main():
     ap.add_argument("--packed", action="store_true")
     ap.add_argument("--expand", action="store_true")
     ap.add_argument("--elems", action="store_true")
+    ap.add_argument("--key-range", default=None, help="FIRST:LAST or auto")
+    ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     args.out = args.out or os.path.join(ROOT, "profiles", "coalesce_elems_ubench.jsonl" if args.elems else
@@ -349,6 +361,11 @@ def main():
         dst = torch.empty(half, dtype=torch.uint8, device="cuda")
         st = torch.cuda.Stream()
         co = Coalescer(0)
+        kr = None
+        if args.key_range:
+            kr = (int(keys.min()), int(keys.max()) + 1) if args.key_range == "auto" else tuple(map(int, args.key_range.split(":")))
+            co.set_key_range(*kr)
+            rel = (dk - kr[0]).to(torch.int32)
         torch.cuda.synchronize()
 
         lm = int(name.split(":")[1]) if "seg:" in name and not args.long_min else args.long_min
@@ -393,6 +410,8 @@ def main():
         per = dict(order=[], heads=[], sum=[], call=[], copy=[], index_add=[])
         if knob:
             per["sum_walk"] = []
+        if kr:
+            per["torch_sort"] = []
         for _ in range(args.rounds):
             t = [coalesce() for _ in range(args.calls)]
             for i, k in enumerate(("order", "heads", "sum")):
@@ -402,9 +421,13 @@ def main():
                 per["sum_walk"].append(statistics.median(coalesce(NEVER)[2] for _ in range(args.calls)))
             per["copy"].append(statistics.median(copy() for _ in range(args.calls)))
             per["index_add"].append(statistics.median(index_add() for _ in range(args.calls)))
+            if kr:
+                with torch.cuda.stream(st):
+                    per["torch_sort"].append(statistics.median(timed(st, lambda: torch.sort(rel, stable=True))
+                                                               for _ in range(args.calls)))
         best = {k: min(v) for k, v in per.items()}
         ln = dict(shape=name, n=n, m=m, cols=cols, row_bytes=row, longest_segment=int(counts.max()),
-                  long_min=lm, route=route,
+                  long_min=lm, route=route, lib=args.label, key_range=kr, order_route=co.order_route() if kr else None,
                   sum_moved_bytes=moved, round_ms={k: [round(x, 4) for x in v] for k, v in per.items()},
                   best_ms={k: round(v, 4) for k, v in best.items()},
                   sum_gbs=round(moved / best["sum"] / 1e6, 1), copy_gbs=round(2 * half / best["copy"] / 1e6, 1),
@@ -416,7 +439,7 @@ def main():
         del dk, vals, kout, vout, inv, inv64, acc, src, dst
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
+    with open(args.out, "a" if args.append else "w") as f:
         for ln in lines:
             f.write(json.dumps(ln) + "\n")
 
