@@ -80,6 +80,7 @@ SIGNATURES = {
     "dml_store_fetch_range": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _P(_i64)]),
     "dml_store_fetch_device": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _P(_i64), _vp]),
     "dml_store_fetch_range_device": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _P(_i64), _vp]),
+    "dml_store_fetch_planes_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "dml_store_write_all": (C.c_int, [_vp, _vp, _i64, _P(_i64)]),
     "dml_store_read_all": (C.c_int, [_vp, _vp, _i64]),
     "dml_store_sync_to": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _P(_i64)]),
@@ -182,6 +183,7 @@ DML_FLAG_NO_SPECULATION = 0x4
 DML_KNOB_IDENT_FULL_MIN_BYTES = 1
 DML_KNOB_INDEX_CUS = 2
 DML_KNOB_FETCH_KERNEL = 3
+DML_KNOB_FETCH_PLANES = 4
 # k_fetch_vec's tile (output bytes per wave instruction / per block)
 DML_FETCH_WAVE_BYTES = 1024
 DML_FETCH_BLOCK_BYTES = 4096

@@ -314,6 +314,16 @@ hipError_t launch_fetch_vec(int vtype, const void* shard, const float* alpha, in
 // Behind a list fetch: *bad (this fetch's lowest bad index) into the sticky verdict, *bad reset.
 hipError_t launch_fetch_verdict(unsigned long long* bad, const int64_t* keys, FetchVerdict* v, hipStream_t st);
 
+// ---- plane fetch (dml_fetch_planes.hip) ----
+// k_fetch_planes / k_fetch_planes_narrow: row j of `values` (and of `alpha_plane`, when given,
+// from `alpha`) = the shard row of keys[j], rows of `rowbytes` bytes; a key outside
+// [first, last] writes nothing and leaves its list index in *bad. `depth` (diagnostic,
+// DML_KNOB_FETCH_PLANES): occurrences in flight per group, 0 = the shipped choice.
+constexpr int kPlanesDepthMax = 4;
+hipError_t launch_fetch_planes(const void* shard, const float* alpha, int64_t rowbytes, const int64_t* keys, int64_t n,
+                               int64_t first, int64_t last, void* values, void* alpha_plane, unsigned long long* bad,
+                               int depth, hipStream_t st);
+
 // ---- diagnostics: synthetic data, streaming ceilings, floors (dml_diag.hip) ----
 hipError_t launch_synth_fill(int vtype, void* p, int64_t n, uint64_t s0, hipStream_t st);
 hipError_t launch_stream(bool copy, void* dst, const void* src, int64_t n16, hipStream_t st, LaunchEv ev);

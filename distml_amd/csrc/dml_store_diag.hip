@@ -188,6 +188,11 @@ int dml_diag_store_knob(dml_store* s, int32_t knob, int64_t value) {
                 return set_err(DML_E_INVALID_ARG, "bad fetch kernel choice");
             s->fetch_kernel = value;
             return DML_OK;
+        case DML_KNOB_FETCH_PLANES:
+            if (value > kPlanesDepthMax || (value & (value - 1)) != 0)
+                return set_err(DML_E_INVALID_ARG, "bad plane fetch depth");
+            s->fetch_planes_depth = value;
+            return DML_OK;
         default: return set_err(DML_E_INVALID_ARG, "unknown knob");
     }
 }

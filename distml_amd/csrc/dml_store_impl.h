@@ -166,6 +166,7 @@ struct dml_store {
     dml::detail::Mirror<dml::FetchVerdict> fver;
     unsigned long long* fbad_dev = nullptr;   // lowest bad list index of the running fetch
     int64_t fetch_kernel = 0;                 // DML_KNOB_FETCH_KERNEL
+    int64_t fetch_planes_depth = 0;           // DML_KNOB_FETCH_PLANES
     // int32 owner apply (dml_store_apply_dense_device): index of the first negative final
     // counter, posted behind every checked apply
     dml::detail::Mirror<unsigned long long> neg;

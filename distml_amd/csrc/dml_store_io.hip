@@ -262,6 +262,8 @@ int dml_store_fetch_range(dml_store* s, int64_t first_key, int64_t last_key, uin
     return fetch_impl(s, nullptr, lo <= hi ? hi - lo + 1 : 0, lo, out, cap, out_len);
 }
 
+static int finish_device_fetch(dml_store* s, const int64_t* dkeys, hipStream_t user);
+
 // The device fetch behind its entry checks (begin_call done: every accepted push retired, so
 // s->data names the shard buffer the last of them wrote). dkeys == nullptr: the range form.
 // The encode, the list form's verdict and the event go on the apply stream; the kernels of
@@ -289,6 +291,12 @@ static int fetch_device_impl(dml_store* s, const int64_t* dkeys, int64_t nkeys, 
         HIPCHK(launch_fetch_vec(vtype_of(s->desc), s->data, alpha, s->cols, dkeys, key_lo, nkeys, s->first, s->last,
                                 (uint8_t*)dev_out, rec, s->K, value_slot, s->fbad_dev, variant, s->stream));
     }
+    return finish_device_fetch(s, dkeys, user);
+}
+
+// Behind a device fetch's kernel on the apply stream (records or planes; dkeys == nullptr: the
+// range form): the verdict, the event, and the caller's wait or the synchronous verdict.
+static int finish_device_fetch(dml_store* s, const int64_t* dkeys, hipStream_t user) {
     // fver.ev is recorded behind every device fetch, and the caller's stream waits for it; only
     // the list form has a verdict to post in front of it
     if (dkeys) {
@@ -334,6 +342,37 @@ int dml_store_fetch_range_device(dml_store* s, int64_t first_key, int64_t last_k
     int slot;
     *out_len = nkeys * fetch_record_bytes(s, &slot);
     return fetch_device_impl(s, nullptr, nkeys, lo, dev_out, cap, out_len, (hipStream_t)stream);
+}
+
+// The coalescer's overlap test (dml_coalesce.hip), on byte extents.
+static bool extents_overlap(const void* a, int64_t alen, const void* b, int64_t blen) {
+    if (!a || !b || alen <= 0 || blen <= 0) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)blen && y < x + (uintptr_t)alen;
+}
+
+int dml_store_fetch_planes_device(dml_store* s, const int64_t* dev_keys, int64_t n, void* dev_values, void* dev_alpha,
+                                  void* stream) {
+    if (int rc = check_store(s)) return rc;
+    Entry in(s);
+    if (int rc = begin_call(s)) return rc;
+    if (n < 0) return set_err(DML_E_INVALID_ARG, "negative key count");
+    if (dev_alpha && !s->adagrad) return set_err(DML_E_INVALID_ARG, "an alpha plane on a store that is not AdaGrad");
+    if (n > 0 && (!dev_keys || !dev_values)) return set_err(DML_E_INVALID_ARG, "null keys or values plane");
+    if (((uintptr_t)dev_keys & 7) != 0) return set_err(DML_E_INVALID_ARG, "fetch keys are not 8-byte aligned");
+    if ((((uintptr_t)dev_values | (uintptr_t)dev_alpha) & 3) != 0)
+        return set_err(DML_E_INVALID_ARG, "fetch plane is not 4-byte aligned");
+    const int64_t cols = s->is_matrix ? s->cols : 1;
+    const int64_t row = cols * s->V, arow = cols * 4;  // a plane row: no fetch slot, no stride flag
+    if (extents_overlap(dev_values, n * row, dev_keys, n * 8) || extents_overlap(dev_alpha, n * arow, dev_keys, n * 8))
+        return set_err(DML_E_INVALID_ARG, "fetch plane overlaps the keys");
+    if (extents_overlap(dev_values, n * row, dev_alpha, n * arow))
+        return set_err(DML_E_INVALID_ARG, "fetch planes overlap");
+    if (n == 0) return DML_OK;
+    if (int rc = ensure_fetch_record(s)) return rc;
+    HIPCHK(launch_fetch_planes(s->data, dev_alpha ? s->alpha : nullptr, row, dev_keys, n, s->first, s->last, dev_values,
+                               dev_alpha, s->fbad_dev, (int)s->fetch_planes_depth, s->stream));
+    return finish_device_fetch(s, dev_keys, (hipStream_t)stream);
 }
 
 // Rows [lo, hi] (local indices), big-endian, row-major: DataOutputStream.write{Float,Int,Double}.

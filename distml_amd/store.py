@@ -323,6 +323,23 @@ class DataStore:
         check(rc, self)
         return out_len.value
 
+    def handleFetchPlanesDevice(self, format: DataDesc, rows: DeviceKeys, values_ptr: int,
+                                alpha_ptr: Optional[int] = None, stream: Optional[int] = None) -> None:
+        """The rows of an occurrence list straight into planes (dml_store_fetch_planes_device):
+        row j of the T[n][cols] at `values_ptr` is the shard row of key j of `rows` (int64 keys
+        on this store's device, repeats and any order allowed), and, on an AdaGrad store, row j
+        of the float[n][cols] at `alpha_ptr` its alpha row (None: values only). Both on this
+        store's device, 4-byte aligned. `stream` as in handleFetchDevice: the call returns at
+        once and that stream waits for the planes; a key outside the shard then raises
+        ArrayIndexOutOfBoundsException from flush() or a later call, with every other row
+        written. None: synchronous, and the call raises."""
+        self._check_format(format)
+        if not isinstance(rows, DeviceKeys):
+            raise TypeError("handleFetchPlanesDevice takes DeviceKeys")
+        check(_lib.load().dml_store_fetch_planes_device(self._h, C.c_void_p(rows.ptr or None), rows.n,
+                                                        C.c_void_p(values_ptr or None), C.c_void_p(alpha_ptr or None),
+                                                        C.c_void_p(stream or None)), self)
+
     def writeAll(self, os=None) -> bytes:
         """Big-endian row-major dump (FloatMatrixStore.java:74-81); writes to `os` if given."""
         n = self._rows * self._cols * np.dtype(self.dtype).itemsize

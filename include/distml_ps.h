@@ -294,6 +294,45 @@ int dml_store_fetch_range_device(dml_store* s, int64_t first_key, int64_t last_k
 #define DML_FETCH_WAVE_BYTES 1024
 #define DML_FETCH_BLOCK_BYTES 4096
 
+/* The rows of an occurrence list straight into per-occurrence planes on the store's device:
+ * what a worker on the store's own GPU wants instead of records (no JNI binding: the Java
+ * API has no device pointers for single stores). One kernel goes shard -> planes
+ * (dml_fetch_planes.hip); nothing is sorted, encoded or expanded.
+ *
+ * dev_keys: int64[n] in device memory, 8-byte aligned; keys may repeat and come in any order.
+ * dev_values: a row-major contiguous T[n][cols], T the store's value type (arrays: cols = 1);
+ * row j holds the shard row of dev_keys[j], byte for byte (bytes pass as dwords, no float
+ * instruction touches them). dev_alpha: FloatMatrixStoreAdaGrad's float[n][cols] alpha plane;
+ * it may be NULL on an AdaGrad store (values only) and must be NULL on every other store.
+ * A plane row is cols x sizeof(T) bytes for every store: FloatArrayStore's 8-byte fetch slot
+ * and DML_FLAG_FLOAT_ARRAY_REF_STRIDE do not appear in a plane. Both planes need the
+ * alignment of a device push and nothing more (4 bytes), and only
+ * [dev_values, + n x cols x sizeof(T)) and [dev_alpha, + n x cols x 4) are ever written, so a
+ * plane may lie between live data.
+ *
+ * Entry, ordering and `stream` are dml_store_fetch_device's: the call first retires every
+ * accepted push and returns a deferred error (a store closed by a negative counter refuses
+ * here); the kernel runs on the store's apply stream and an event is recorded behind it; a
+ * non-null `stream` waits for that event and the call returns at once, stream == NULL makes
+ * the call synchronous. A fetch sees every push accepted before it and none accepted after
+ * it, with no flush in between.
+ *
+ * DML_E_INVALID_ARG, with nothing launched and no store state changed: n < 0; a null dev_keys
+ * or dev_values with n > 0; dev_keys not 8-byte aligned; dev_values or dev_alpha not 4-byte
+ * aligned; a dev_alpha on a store that is not AdaGrad; a plane whose n rows overlap the n
+ * keys or the other plane's n rows. n == 0 returns DML_OK with nothing launched.
+ *
+ * Keys are checked on the device as 64-bit values (first <= key <= last). A key outside the
+ * shard is never turned into an address and no byte of its row is written in either plane;
+ * every other row is written. The lowest list index of such a key comes home as in
+ * dml_store_fetch_device: stream == NULL returns DML_E_KEY_OUT_OF_SHARD from the call
+ * itself, otherwise the flush or the next read of the store returns it; the store's error
+ * state holds that key and col -1 until dml_store_clear_error.
+ *
+ * There is no range form: a range of rows as a plane is the shard itself (dml_store_device_ptr). */
+int dml_store_fetch_planes_device(dml_store* s, const int64_t* dev_keys, int64_t n,
+                                  void* dev_values, void* dev_alpha, void* stream);
+
 /* writeAll/readAll (FloatMatrixStore.java:74-91 etc.): big-endian row-major
  * values, the bytes DataOutputStream.writeFloat/writeInt/writeDouble emit.
  * read_all assigns the elements the stream holds before failing with
@@ -1192,6 +1231,10 @@ int dml_diag_pull_kernels(const int64_t* dev_keys, int64_t nkeys, int64_t total_
  * dword gathered singly, 2 = 16-byte loads; 1024: blocks renumbered XCD-contiguous;
  * 2048 / 4096: one / four vectors per thread); the bytes are the same for every value. */
 #define DML_KNOB_FETCH_KERNEL 3
+/* DML_KNOB_FETCH_PLANES: occurrences a group (k_fetch_planes) or a thread
+ * (k_fetch_planes_narrow) of dml_store_fetch_planes_device keeps in flight: 1, 2 or 4;
+ * 0 (the default) = the shipped choice. The bytes are the same for every value. */
+#define DML_KNOB_FETCH_PLANES 4
 int dml_diag_store_knob(dml_store* s, int32_t knob, int64_t value);
 
 /* The partition plan an array store makes for one chunk before any kernel runs (diagnostic /
