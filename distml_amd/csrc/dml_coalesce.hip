@@ -30,6 +30,9 @@
 // dml_coalesce_pack_device runs the same kernels with the sum kernels in their record form
 // (REC): the sums go straight into push records, key in front, and no dense plane exists.
 //
+// dml::co_push_planes (dml_store_push_planes_device) runs the order, heads and count here and
+// hands the sum to dml_push_planes.hip, whose kernels apply it to a store's shard (PushSink).
+//
 // A segment of the context's long_min occurrences and more is left out by both walks and
 // summed by dml_coalesce_long.hip's kernels instead: the same adds in the same order.
 #include <hipcub/hipcub.hpp>
@@ -327,6 +330,7 @@ struct dml_coalescer {
     uint32_t* count_dev = nullptr;  // k_co_offsets' total
     uint32_t* count_host = nullptr; // ... copied here (pinned); the one word the host waits for
     hipEvent_t done = nullptr;      // the last call's last kernel
+    hipEvent_t handoff = nullptr;   // plane push: the caller's stream, where the store's apply stream takes over
     bool in_flight = false;
     hipEvent_t ev[6] = {};          // stage boundaries of the last call (dml_diag_coalesce_times)
     bool timed = false, timed_sum = false;
@@ -349,6 +353,7 @@ extern "C" int dml_coalescer_create(int32_t device, dml_coalescer** out) {
     if (e == hipSuccess) e = hipMemset(c->count_dev, 0, 256);  // the flag word differs from every epoch
     if (e == hipSuccess) e = hipHostMalloc((void**)&c->count_host, 64, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->handoff, hipEventDisableTiming);
     for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipEventCreate(&c->ev[i]);
     if (e != hipSuccess) {
         const int rc = set_error(e == hipErrorOutOfMemory ? DML_E_NOMEM : DML_E_HIP,
@@ -368,6 +373,7 @@ extern "C" void dml_coalescer_destroy(dml_coalescer* c) {
     if (c->count_dev) (void)hipFree(c->count_dev);
     if (c->count_host) (void)hipHostFree(c->count_host);
     if (c->done) (void)hipEventDestroy(c->done);
+    if (c->handoff) (void)hipEventDestroy(c->handoff);
     for (hipEvent_t e : c->ev)
         if (e) (void)hipEventDestroy(e);
     delete c;
@@ -394,7 +400,8 @@ struct CoElems {
 };
 
 int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t* dev_keys, int64_t n,
-           const void* dev_values, const CoElems* el, const CoOut& o, int64_t* out_rows, void* stream);
+           const void* dev_values, const CoElems* el, const CoOut& o, int64_t* out_rows, void* stream,
+           const PushSink* sk = nullptr);
 
 }  // namespace
 
@@ -562,11 +569,16 @@ namespace {
 
 // The device side of the three calls, after their argument checks. The sum is dense or
 // record (`o`) over rows (`dev_values`) or over element updates (`el`; then `rowbytes` is the
-// output row's).
+// output row's). `sk` (co_push_planes): the sink is a store; `o` then names no output, the
+// distinct keys stay in the workspace, and the sum kernels, the store's verdict and `done` go
+// on sk->apply behind an event of `stream` (a null `stream`: every stage runs on sk->apply,
+// and the caller synchronises).
 int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t* dev_keys, int64_t n,
-           const void* dev_values, const CoElems* el, const CoOut& o, int64_t* out_rows, void* stream) {
+           const void* dev_values, const CoElems* el, const CoOut& o, int64_t* out_rows, void* stream,
+           const PushSink* sk) {
     DeviceGuard g(c->device);
     hipStream_t st = (hipStream_t)stream;
+    if (sk && !st) st = sk->apply;
     if (c->in_flight) {  // one call in flight per context
         HIPCHK(hipEventSynchronize(c->done));
         c->in_flight = false;
@@ -581,7 +593,7 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
     const uint32_t lmin = (uint32_t)std::min<int64_t>(c->long_min, (int64_t)1 << 31);
     const int64_t nlong = dev_values || el ? n / lmin : 0;  // the most long segments n occurrences hold
     const bool rec = o.rec_bytes != 0;
-    const size_t ukeys = rec && !o.keys_out ? (size_t)n * 8 : 0;  // the record form reads the keys back
+    const size_t ukeys = (rec || sk) && !o.keys_out ? (size_t)n * 8 : 0;  // the record form and the sink read the keys back
     // kin | kout | vin | vout | seg | blockoff | long list | unique keys | sort temp
     const size_t o_kin = 0, o_kout = o_kin + up256((size_t)n * 8), o_vin = o_kout + up256((size_t)n * 8),
                  o_vout = o_vin + up256((size_t)n * 4), o_seg = o_vout + up256((size_t)n * 4),
@@ -681,6 +693,32 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c->ev[5], st));
         c->timed_sum = true;
+    } else if (sk) {
+        PushP a;
+        a.values = (const uint8_t*)dev_values;
+        a.idx = vout;
+        a.seg = seg;
+        a.ukeys = keys_out;
+        a.n = n;
+        a.m = m;
+        a.rowbytes = rowbytes;
+        a.nspan = (rowbytes + kCoSpanBytes - 1) / kCoSpanBytes;
+        const int64_t nvec = std::min<int64_t>((rowbytes + 15) / 16, 64);
+        a.lgG = 0;
+        while (((int64_t)1 << a.lgG) < nvec) ++a.lgG;
+        a.lmin = lmin;
+        a.list = (uint32_t*)(c->ws + o_list);
+        a.route = c->count_dev + kRouteWord;
+        a.sink = *sk;
+        a.cand = sk->cand;
+        if (st != sk->apply) {  // the inputs and the order are complete on `st`: no host wait
+            HIPCHK(hipEventRecord(c->handoff, st));
+            HIPCHK(hipStreamWaitEvent(sk->apply, c->handoff, 0));
+        }
+        HIPCHK(launch_push_planes(a, d.value_type, nlong > 0, sk->apply));
+        HIPCHK(launch_fetch_verdict(sk->bad, keys_out, const_cast<FetchVerdict*>(sk->verdict), sk->apply));
+        HIPCHK(hipEventRecord(c->ev[5], sk->apply));
+        c->timed_sum = true;
     } else if (dev_values) {
         SumP a;
         a.values = (const uint8_t*)dev_values;
@@ -727,7 +765,7 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
         c->timed_sum = true;
     }
     c->timed = true;
-    HIPCHK(hipEventRecord(c->done, st));
+    HIPCHK(hipEventRecord(c->done, sk ? sk->apply : st));
     c->in_flight = true;
     if (!st) {
         HIPCHK(hipStreamSynchronize(st));
@@ -737,6 +775,17 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
 }
 
 }  // namespace
+
+int dml::co_device(const dml_coalescer* c) { return c->device; }
+
+int dml::co_push_planes(dml_coalescer* c, int32_t value_type, int64_t rowbytes, const int64_t* dev_keys, int64_t n,
+                        const void* dev_values, const PushSink& sk, void* stream) {
+    dml_desc d{};
+    d.value_type = value_type;
+    const CoOut o = {nullptr, nullptr, nullptr, n, 0, 0, 0, nullptr};  // no output: m <= n always fits
+    int64_t m = 0;
+    return co_run(c, d, rowbytes, dev_keys, n, dev_values, nullptr, o, &m, stream, &sk);
+}
 
 extern "C" int dml_diag_coalesce_times(dml_coalescer* c, float* ms3) {
     if (!c || !ms3) return set_error(DML_E_INVALID_ARG, "null coalescer or ms3");

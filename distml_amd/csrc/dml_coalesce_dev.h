@@ -2,8 +2,9 @@
 // heads and the walk k_co_sum; dml_coalesce_long.hip: the long-segment list and its sum
 // kernels; dml_coalesce_elems.hip: the element-update sum; dml_coalesce_order.hip: the order
 // stage for keys in a declared range): the one add
-// of the contract, the narrow row load, the record form's parameters and the long path's and
-// the element sum's launches. Device and host; not part of the public ABI.
+// of the contract, the narrow row load, the record form's parameters, the long path's and
+// the element sum's launches, and the store-sink form of the sum (dml_push_planes.hip,
+// §4.17). Device and host; not part of the public ABI.
 #pragma once
 #include "distml_ps.h"
 #include "dml_fetch_line.h"
@@ -146,6 +147,29 @@ struct OrderP {
     uint32_t* flag;
     uint32_t epoch;
 };
+// The sum with a store's shard as its sink (dml_push_planes.hip; dml_store_push_planes_device,
+// DESIGN.md §4.17): key u's sums are applied to shard row ukeys[u] - first by the store's own
+// element update instead of being written anywhere. co_run fills the coalescer's side, the
+// store's side comes from its PushSink (dml_internal.h).
+struct PushP {
+    const uint8_t* values;  // T[n][cols], 4-byte aligned
+    const uint32_t* idx;    // occurrence indices, sorted by key, list order inside a key
+    const uint32_t* seg;    // seg[u]: the first sorted position of unique key u
+    const int64_t* ukeys;   // the distinct keys, ascending
+    int64_t n, m;
+    int64_t rowbytes;
+    int64_t nspan;          // 1-KiB spans of a row
+    int32_t lgG;            // log2 of the lanes of a group
+    uint32_t lmin;          // a segment of lmin occurrences and more is the long kernels'
+    const uint32_t* list;   // the long keys' u (k_co_long_list)
+    const uint32_t* route;
+    PushSink sink;
+    DeltaCand* cand;        // AdaGrad: this launch's candidates, one per block
+};
+// has_long: k_co_long_list and the long kernels first; then the walk (or its narrow form);
+// AdaGrad: the candidates' finalize behind them.
+hipError_t launch_push_planes(const PushP& a, int32_t value_type, bool has_long, hipStream_t st);
+
 int co_order_passes(uint64_t span);
 size_t co_order_count_bytes();
 void co_launch_order(const OrderP& o, hipStream_t st);

@@ -8,6 +8,7 @@
 #include <string>
 
 struct dml_store;
+struct dml_coalescer;
 
 namespace dml {
 
@@ -323,6 +324,37 @@ constexpr int kPlanesDepthMax = 4;
 hipError_t launch_fetch_planes(const void* shard, const float* alpha, int64_t rowbytes, const int64_t* keys, int64_t n,
                                int64_t first, int64_t last, void* values, void* alpha_plane, unsigned long long* bad,
                                int depth, hipStream_t st);
+
+// ---- plane push (dml_push_planes.hip; dml_store_push_planes_device) ----
+// The store's side of a plane push: the shard the coalescer's sums are applied to, on the
+// store's apply stream. `bad` takes the lowest refused distinct-key index of the call and
+// `verdict` is the store's sticky fetch verdict: a closed one turns the call's kernels into
+// no-ops (a push behind a failed one applies nothing), and co_push_planes posts this call's
+// behind its kernels (launch_fetch_verdict over the distinct keys).
+struct PushSink {
+    uint8_t* data;  // rows x rowbytes
+    float* delta;   // AdaGrad (md != null): the delta and alpha arrays, cand of kPushCands, the running record
+    float* alpha;
+    DeltaCand* cand;
+    MaxDelta* md;
+    float initial_alpha, min_alpha, factor;
+    int64_t first, last;
+    int32_t cols;
+    unsigned long long* bad;
+    const FetchVerdict* verdict;
+    hipStream_t apply;
+};
+// AdaGrad candidates of one call: the walk's blocks, then the long kernels'.
+constexpr int kPushWalkCands = 1536, kPushLongCands = 512, kPushCands = kPushWalkCands + kPushLongCands;
+// dml_coalesce.hip: order, heads and count of (dev_keys, n) on `stream` (null: on sk.apply),
+// then the sums into the sink on sk.apply behind an event of `stream`. Arguments checked by
+// the caller (dml_store_push_planes_device); `rowbytes` and `value_type` are the store's.
+int co_device(const dml_coalescer* c);
+int co_push_planes(dml_coalescer* c, int32_t value_type, int64_t rowbytes, const int64_t* dev_keys, int64_t n,
+                   const void* dev_values, const PushSink& sk, void* stream);
+// k_maxdelta_elems alone (dml_moments.hip): n element-index candidates against the running record.
+hipError_t launch_maxdelta_elems(const DeltaCand* cand, int64_t n, MaxDelta* md, int64_t first, int32_t cols,
+                                 hipStream_t st);
 
 // ---- diagnostics: synthetic data, streaming ceilings, floors (dml_diag.hip) ----
 hipError_t launch_synth_fill(int vtype, void* p, int64_t n, uint64_t s0, hipStream_t st);

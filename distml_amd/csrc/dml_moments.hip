@@ -198,6 +198,12 @@ __global__ __launch_bounds__(256) void k_maxdelta_elems(const DeltaCand* __restr
     }
 }
 
+hipError_t launch_maxdelta_elems(const DeltaCand* cand, int64_t n, MaxDelta* md, int64_t first, int32_t cols,
+                                 hipStream_t st) {
+    hipLaunchKernelGGL(k_maxdelta_elems, dim3(1), dim3(256), 0, st, cand, n, md, first, cols);
+    return hipGetLastError();
+}
+
 hipError_t launch_ada_moments(float* shard, const float* src, int64_t rows, int32_t cols, const AdaArgs& ada,
                               MaxDelta* md, int64_t first, hipStream_t st, LaunchEv ev) {
     if (cols % 4 || rows <= 0) return hipErrorInvalidValue;

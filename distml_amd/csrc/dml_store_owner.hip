@@ -1,6 +1,7 @@
 // dml_store_owner.hip — what a shard group drives on an owner's store: the applies and
 // commits of slices that arrive in HBM (dml_store_apply_dense_device, dml_store_assign_*_device,
-// dml_store_apply_adagrad_moments_device) and the dml::store_* calls of dml_group.hip. Pushes
+// dml_store_apply_adagrad_moments_device), the plane push of a worker on the store's own GPU
+// (dml_store_push_planes_device) and the dml::store_* calls of dml_group.hip. Pushes
 // before them are retired first; an earlier call's verdict is read only once it has landed.
 #include "dml_store_impl.h"
 
@@ -87,6 +88,64 @@ int dml_store_apply_dense_device(dml_store* s, const void* dev_src, int64_t elem
         s->ev_used.push_back(ev);
     }
     return DML_OK;
+}
+
+// The plane push (dml_push_planes.hip): refusals first, with nothing changed;
+// then the owner applies' entry; then the coalescer's order stage on the caller's stream and the
+// sums into the shard on the apply stream (dml::co_push_planes).
+int dml_store_push_planes_device(dml_store* s, dml_coalescer* c, const int64_t* dev_keys, int64_t n,
+                                 const void* dev_values, void* stream) {
+    if (int rc = check_store(s)) return rc;
+    if (!c) return set_err(DML_E_INVALID_ARG, "null coalescer");
+    Entry in(s);
+    if (n < 0) return set_err(DML_E_INVALID_ARG, "negative occurrence count");
+    if (n > 0x7FFFFFFFll) return set_err(DML_E_INVALID_ARG, "lists of 2^31 occurrences and more");
+    if (n > 0 && (!dev_keys || !dev_values)) return set_err(DML_E_INVALID_ARG, "null keys or values plane");
+    if (((uintptr_t)dev_keys & 7) != 0) return set_err(DML_E_INVALID_ARG, "push keys are not 8-byte aligned");
+    if (((uintptr_t)dev_values & 3) != 0) return set_err(DML_E_INVALID_ARG, "push plane is not 4-byte aligned");
+    if (co_device(c) != s->device) return set_err(DML_E_INVALID_ARG, "the coalescer belongs to another device");
+    if (s->is_matrix && !s->desc.dense_column)
+        return set_err(DML_E_UNSUPPORTED, "sparse-column matrix rows are not supported (SURVEY defect 3)");
+    if (vtype_of(s->desc) == kI32)
+        return set_err(DML_E_UNSUPPORTED, "plane pushes into int32 stores: their checked adds need a rollback");
+    if (int rc = retire_all(s)) return rc;
+    if (int rc = collect_apply_check(s, false)) return rc;
+    if (int rc = failed(s)) return rc;
+    if (n == 0) return DML_OK;
+    if (!s->fbad_dev) {  // the running call's lowest refused index, then the sticky verdict: a device fetch's
+        HIPCHK(hipMalloc((void**)&s->fbad_dev, sizeof(unsigned long long)));
+        HIPCHK(hipMemsetAsync(s->fbad_dev, 0xFF, sizeof(unsigned long long), s->stream));
+    }
+    if (int rc = s->fver.ensure(s->stream)) return rc;
+    if (s->adagrad && s->cand_n < kPushCands) {  // one candidate per block of the call's kernels
+        HIPCHK(hipStreamSynchronize(s->stream));
+        HIPCHK(hipFree(s->cand));
+        s->cand = nullptr;
+        s->cand_n = 0;
+        HIPCHK(hipMalloc((void**)&s->cand, sizeof(DeltaCand) * (size_t)(kPushCands + kMdParts)));
+        s->cand_n = kPushCands;
+    }
+    const int64_t cols = s->is_matrix ? s->cols : 1;
+    PushSink sk{};
+    sk.data = (uint8_t*)s->data;
+    sk.delta = s->delta;
+    sk.alpha = s->alpha;
+    sk.cand = s->cand;
+    sk.md = s->adagrad ? s->md : nullptr;
+    sk.initial_alpha = s->initial_alpha;
+    sk.min_alpha = s->min_alpha;
+    sk.factor = s->factor;
+    sk.first = s->first;
+    sk.last = s->last;
+    sk.cols = (int32_t)cols;
+    sk.bad = s->fbad_dev;
+    sk.verdict = s->fver.dev;
+    sk.apply = s->stream;
+    if (int rc = co_push_planes(c, vtype_of(s->desc), cols * s->V, dev_keys, n, dev_values, sk, stream)) return rc;
+    if (int rc = s->fver.post(s->stream)) return rc;
+    if (stream) return DML_OK;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return collect_fetch_check(s, true);
 }
 
 int dml_store_assign_dense_device(dml_store* s, const void* dev_src, int64_t elems) {

@@ -340,6 +340,27 @@ class DataStore:
                                                         C.c_void_p(values_ptr or None), C.c_void_p(alpha_ptr or None),
                                                         C.c_void_p(stream or None)), self)
 
+    def handlePushPlanesDevice(self, format: DataDesc, coalescer: "Coalescer", rows: DeviceKeys, values_ptr: int,
+                               stream: Optional[int] = None) -> None:
+        """A gradient plane straight into the shard (dml_store_push_planes_device): what
+        pushDevice of coalescer.run_packed(rows, values) leaves, with no record in between. `rows`
+        are the occurrence keys (int64 on this store's device, repeats and any order allowed) and
+        row j of the T[n][cols] at `values_ptr` (4-byte aligned) is occurrence j's update. Per
+        distinct key the rows are summed in list order from +0.0 and the sum is applied by the
+        store's own update. `coalescer` (this device's) supplies the order stage, its declared key
+        range and long_min. `stream` is the raw hipStream_t on which both inputs are complete: the
+        call returns without waiting for the apply, both inputs must stay valid until flush() or a
+        read of the store, and a key outside the shard raises ArrayIndexOutOfBoundsException from
+        there. None: synchronous, and the call raises. FloatMatrixStore, DoubleMatrixStore,
+        FloatMatrixStoreAdaGrad, FloatArrayStore and DoubleArrayStore; int32 stores raise."""
+        self._check_format(format)
+        if not isinstance(rows, DeviceKeys):
+            raise TypeError("handlePushPlanesDevice takes DeviceKeys")
+        if not isinstance(coalescer, Coalescer):
+            raise TypeError("handlePushPlanesDevice takes a Coalescer")
+        check(_lib.load().dml_store_push_planes_device(self._h, coalescer._h, C.c_void_p(rows.ptr or None), rows.n,
+                                                       C.c_void_p(values_ptr or None), C.c_void_p(stream or None)), self)
+
     def writeAll(self, os=None) -> bytes:
         """Big-endian row-major dump (FloatMatrixStore.java:74-81); writes to `os` if given."""
         n = self._rows * self._cols * np.dtype(self.dtype).itemsize

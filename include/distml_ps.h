@@ -333,6 +333,54 @@ int dml_store_fetch_range_device(dml_store* s, int64_t first_key, int64_t last_k
 int dml_store_fetch_planes_device(dml_store* s, const int64_t* dev_keys, int64_t n,
                                   void* dev_values, void* dev_alpha, void* stream);
 
+/* A gradient plane straight into the shard on the store's device: the push half of the same
+ * worker (no JNI binding, for the same reason). What the store holds afterwards, data, AdaGrad's
+ * delta, alpha and maxDelta (value, row, col) and the error state, is byte for byte what
+ * dml_coalesce_pack_device(c, desc, cols, 0, dev_keys, n, dev_values, ...) followed by
+ * dml_store_push_batch_device of those records leaves; no record and no sum is ever written
+ * (dml_push_planes.hip).
+ *
+ * dev_keys: int64[n] in device memory, 8-byte aligned; keys may repeat and come in any order.
+ * dev_values: a row-major contiguous T[n][cols], T and cols the store's (arrays: cols = 1),
+ * 4-byte aligned; only its n rows are read. c supplies the order stage, the workspace, the
+ * declared key range and long_min exactly as for dml_coalesce_pack_device, and must belong to
+ * the store's device; one call is in flight per coalescer. Per distinct key, ascending, one
+ * update row is formed, element i = ((+0.0 + v[j1][i]) + v[j2][i]) + ... over the key's
+ * occurrences in list order, one IEEE rounding per add; the store's own per-element update then
+ * applies it (plain: row[i] + u; AdaGrad: also delta += u x u, alpha where delta ends above 1,
+ * maxDelta by the reference's strict > in ascending row-major order). A row no key lists is
+ * neither read nor written.
+ *
+ * Served: FloatMatrixStore, DoubleMatrixStore, FloatMatrixStoreAdaGrad (dense column),
+ * FloatArrayStore, DoubleArrayStore. DML_E_UNSUPPORTED: IntMatrixStore and IntArrayStore (their
+ * checked adds need the first-negative verdict and a rollback) and sparse-column stores.
+ *
+ * Entry is dml_store_apply_dense_device's: every accepted push is retired and a deferred error
+ * returned. The kernels that touch the shard run on the store's apply stream, behind every
+ * accepted push and before every later push and fetch, with no flush in between. A non-null
+ * `stream` is the stream on which dev_keys and dev_values are complete: the order stage runs
+ * there (with the coalescer's one host wait for the distinct count), the apply stream waits for
+ * an event recorded there, and the call returns without waiting for the apply; both inputs must
+ * stay valid until the apply stream has passed the call (dml_store_flush or any read of the
+ * store). stream == NULL makes the call synchronous.
+ *
+ * Keys are checked on the device as 64-bit values (first <= key <= last) and a key outside the
+ * shard is never turned into an address. As on the record route, where the reference stops at
+ * the first bad record of the ascending push: if the list's smallest key is below first nothing
+ * is applied, otherwise every key inside the shard is applied. Either way the store's sticky
+ * error becomes DML_E_KEY_OUT_OF_SHARD with the lowest bad key and col -1, returned by the call
+ * itself when stream == NULL and otherwise by the flush or the next read of the store; a plane
+ * push queued behind it before it is reported applies nothing. One difference from the record
+ * route: a store with 4-byte keys compares the whole 64-bit key here, not its (int) cast.
+ *
+ * DML_E_INVALID_ARG, before anything is launched and with no store or coalescer state changed:
+ * a null s or c; n < 0 or n >= 2^31; a null dev_keys or dev_values with n > 0; dev_keys not
+ * 8-byte aligned; dev_values not 4-byte aligned; a coalescer of another device. The unsupported
+ * stores are refused at the same point. n == 0 returns DML_OK with nothing launched. */
+struct dml_coalescer;
+int dml_store_push_planes_device(dml_store* s, struct dml_coalescer* c, const int64_t* dev_keys, int64_t n,
+                                 const void* dev_values, void* stream);
+
 /* writeAll/readAll (FloatMatrixStore.java:74-91 etc.): big-endian row-major
  * values, the bytes DataOutputStream.writeFloat/writeInt/writeDouble emit.
  * read_all assigns the elements the stream holds before failing with
