@@ -82,6 +82,7 @@ SIGNATURES = {
     "dml_store_fetch_range_device": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _P(_i64), _vp]),
     "dml_store_fetch_planes_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "dml_store_push_planes_device": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "dml_store_push_elems_device": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "dml_store_write_all": (C.c_int, [_vp, _vp, _i64, _P(_i64)]),
     "dml_store_read_all": (C.c_int, [_vp, _vp, _i64]),
     "dml_store_sync_to": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _P(_i64)]),

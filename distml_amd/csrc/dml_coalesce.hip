@@ -32,6 +32,8 @@
 //
 // dml::co_push_planes (dml_store_push_planes_device) runs the order, heads and count here and
 // hands the sum to dml_push_planes.hip, whose kernels apply it to a store's shard (PushSink).
+// dml::co_push_elems (dml_store_push_elems_device) does the same for element updates into an
+// int32 store's checked adds (dml_push_elems.hip, ElemSink).
 //
 // A segment of the context's long_min occurrences and more is left out by both walks and
 // summed by dml_coalesce_long.hip's kernels instead: the same adds in the same order.
@@ -401,7 +403,7 @@ struct CoElems {
 
 int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t* dev_keys, int64_t n,
            const void* dev_values, const CoElems* el, const CoOut& o, int64_t* out_rows, void* stream,
-           const PushSink* sk = nullptr);
+           const PushSink* sk = nullptr, const ElemSink* es = nullptr);
 
 }  // namespace
 
@@ -569,16 +571,17 @@ namespace {
 
 // The device side of the three calls, after their argument checks. The sum is dense or
 // record (`o`) over rows (`dev_values`) or over element updates (`el`; then `rowbytes` is the
-// output row's). `sk` (co_push_planes): the sink is a store; `o` then names no output, the
+// output row's). `sk` (co_push_planes) or `es` (co_push_elems): the sink is a store; `o` then names no output, the
 // distinct keys stay in the workspace, and the sum kernels, the store's verdict and `done` go
-// on sk->apply behind an event of `stream` (a null `stream`: every stage runs on sk->apply,
+// on its apply stream behind an event of `stream` (a null `stream`: every stage runs there,
 // and the caller synchronises).
 int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t* dev_keys, int64_t n,
            const void* dev_values, const CoElems* el, const CoOut& o, int64_t* out_rows, void* stream,
-           const PushSink* sk) {
+           const PushSink* sk, const ElemSink* es) {
     DeviceGuard g(c->device);
     hipStream_t st = (hipStream_t)stream;
-    if (sk && !st) st = sk->apply;
+    const hipStream_t apply = sk ? sk->apply : es ? es->apply : nullptr;  // a store sink's stream
+    if ((sk || es) && !st) st = apply;
     if (c->in_flight) {  // one call in flight per context
         HIPCHK(hipEventSynchronize(c->done));
         c->in_flight = false;
@@ -593,7 +596,7 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
     const uint32_t lmin = (uint32_t)std::min<int64_t>(c->long_min, (int64_t)1 << 31);
     const int64_t nlong = dev_values || el ? n / lmin : 0;  // the most long segments n occurrences hold
     const bool rec = o.rec_bytes != 0;
-    const size_t ukeys = (rec || sk) && !o.keys_out ? (size_t)n * 8 : 0;  // the record form and the sink read the keys back
+    const size_t ukeys = (rec || sk || es) && !o.keys_out ? (size_t)n * 8 : 0;  // the record form and the sink read the keys back
     // kin | kout | vin | vout | seg | blockoff | long list | unique keys | sort temp
     const size_t o_kin = 0, o_kout = o_kin + up256((size_t)n * 8), o_vin = o_kout + up256((size_t)n * 8),
                  o_vout = o_vin + up256((size_t)n * 4), o_seg = o_vout + up256((size_t)n * 4),
@@ -672,7 +675,33 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
                        (const uint32_t*)vout, n, boff, keys_out, seg, o.inverse);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev[4], st));
-    if (el) {
+    if (el && es) {
+        PushElemsP a;
+        a.e.cols = el->cols;
+        a.e.vals = el->vals;
+        a.e.idx = vout;
+        a.e.seg = seg;
+        a.e.out = nullptr;
+        a.e.n = n;
+        a.e.m = m;
+        a.e.rowbytes = rowbytes;
+        a.e.nslice = co_elems_slices(el->ncols);
+        a.e.ncols = el->ncols;
+        a.e.per = el->per;
+        a.e.lmin = lmin;
+        a.e.list = (uint32_t*)(c->ws + o_list);
+        a.e.route = c->count_dev + kRouteWord;
+        a.e.rec = RecP{};
+        a.ukeys = keys_out;
+        a.sink = *es;
+        if (st != apply) {  // the inputs and the order are complete on `st`: no host wait
+            HIPCHK(hipEventRecord(c->handoff, st));
+            HIPCHK(hipStreamWaitEvent(apply, c->handoff, 0));
+        }
+        HIPCHK(launch_push_elems(a, nlong > 0, apply));
+        HIPCHK(hipEventRecord(c->ev[5], apply));
+        c->timed_sum = true;
+    } else if (el) {
         ElemsP a;
         a.cols = el->cols;
         a.vals = el->vals;
@@ -765,7 +794,7 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
         c->timed_sum = true;
     }
     c->timed = true;
-    HIPCHK(hipEventRecord(c->done, sk ? sk->apply : st));
+    HIPCHK(hipEventRecord(c->done, apply ? apply : st));
     c->in_flight = true;
     if (!st) {
         HIPCHK(hipStreamSynchronize(st));
@@ -785,6 +814,16 @@ int dml::co_push_planes(dml_coalescer* c, int32_t value_type, int64_t rowbytes, 
     const CoOut o = {nullptr, nullptr, nullptr, n, 0, 0, 0, nullptr};  // no output: m <= n always fits
     int64_t m = 0;
     return co_run(c, d, rowbytes, dev_keys, n, dev_values, nullptr, o, &m, stream, &sk);
+}
+
+int dml::co_push_elems(dml_coalescer* c, const int64_t* dev_keys, int64_t n, int32_t per_occ, const int32_t* dev_cols,
+                       const int32_t* dev_vals, const ElemSink& sk, void* stream) {
+    dml_desc d{};
+    d.value_type = DML_ELEMENT_TYPE_INT;
+    const CoOut o = {nullptr, nullptr, nullptr, n, 0, 0, 0, nullptr};  // no output: m <= n always fits
+    const CoElems el = {dev_cols, dev_vals, sk.cols, per_occ};
+    int64_t m = 0;
+    return co_run(c, d, 4 * (int64_t)sk.cols, dev_keys, n, nullptr, &el, o, &m, stream, nullptr, &sk);
 }
 
 extern "C" int dml_diag_coalesce_times(dml_coalescer* c, float* ms3) {

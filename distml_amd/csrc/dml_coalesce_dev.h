@@ -129,6 +129,40 @@ int64_t co_elems_slices(int32_t ncols);
 // has_long: k_co_long_list and k_co_elems_long first; then k_co_elems. `rec`: their record form.
 void co_launch_elems(const ElemsP& a, bool rec, bool has_long, hipStream_t st);
 
+// ---- the element sum's LDS slice, shared with the element push (dml_push_elems.hip) ----
+// Between two phases of a wave's work on its slice: the compiler keeps the LDS operations
+// on either side in program order (the hardware runs one wave's in issue order).
+__device__ inline void wave_phase() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ inline void zero_slice(uint32_t* sl, uint32_t w, uint32_t t, uint32_t nt) {
+    const u32x4 zero = {0u, 0u, 0u, 0u};
+    for (uint32_t v = t; 4 * v < w; v += nt) ((u32x4*)sl)[v] = zero;
+}
+
+// One element: sl[col - c0] += val when col lies in [c0, c0 + w). c0 + w <= cols < 2^31, so
+// the unsigned difference is under w for exactly those columns, negative ones included.
+__device__ inline void add_elem(uint32_t* sl, uint32_t col, uint32_t val, uint32_t c0, uint32_t w) {
+    const uint32_t c = col - c0;
+    if (c < w) (void)__hip_atomic_fetch_add(sl + c, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// Occurrence j's per_occ elements: pairs by 8-byte loads, an odd last one alone.
+__device__ inline void add_occ(uint32_t* sl, const ElemsP& a, uint32_t j, uint32_t c0, uint32_t w) {
+    const uint32_t* cp = (const uint32_t*)a.cols + (int64_t)j * a.per;
+    const uint32_t* vp = (const uint32_t*)a.vals + (int64_t)j * a.per;
+    int e = 0;
+    for (; e + 2 <= a.per; e += 2) {
+        const u32x2 c = ldg8(cp + e), v = ldg8(vp + e);
+        add_elem(sl, c.x, v.x, c0, w);
+        add_elem(sl, c.y, v.y, c0, w);
+    }
+    if (e < a.per) add_elem(sl, cp[e], vp[e], c0, w);
+}
+
 // The order stage for keys declared to lie in [first, first + span), 1 <= span <= 2^32
 // (dml_coalesce_order.hip; dml_coalescer_set_key_range): kout[i] = key ^ sign bit and
 // vout[i] = occurrence index, by key and then by list position, what the library sort leaves.
@@ -169,6 +203,17 @@ struct PushP {
 // has_long: k_co_long_list and the long kernels first; then the walk (or its narrow form);
 // AdaGrad: the candidates' finalize behind them.
 hipError_t launch_push_planes(const PushP& a, int32_t value_type, bool has_long, hipStream_t st);
+
+// The element sum with an int32 store's shard as its sink (dml_push_elems.hip;
+// dml_store_push_elems_device). `e.out` and `e.rec` are unused; `e.cols` null:
+// the array form.
+struct PushElemsP {
+    ElemsP e;
+    const int64_t* ukeys;  // the distinct keys, ascending
+    ElemSink sink;
+};
+// has_long: k_co_long_list first. The apply kernels, their undo forms, then the verdict.
+hipError_t launch_push_elems(const PushElemsP& a, bool has_long, hipStream_t st);
 
 int co_order_passes(uint64_t span);
 size_t co_order_count_bytes();

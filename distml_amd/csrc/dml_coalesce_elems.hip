@@ -44,39 +44,6 @@ constexpr int kElLongMaxBlocks = 2048;
 static_assert(kElSlice % 256 == 0 && kElSlice >= 1000 && kElWaves * kElSlice * 4 <= 65536,
               "a slice is whole 1-KiB runs, holds config 5's row, and a block's slices fit LDS");
 
-// Between two phases of a wave's work on its slice: the compiler keeps the LDS operations
-// on either side in program order (the hardware runs one wave's in issue order).
-__device__ inline void wave_phase() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ inline void zero_slice(uint32_t* sl, uint32_t w, uint32_t t, uint32_t nt) {
-    const u32x4 zero = {0u, 0u, 0u, 0u};
-    for (uint32_t v = t; 4 * v < w; v += nt) ((u32x4*)sl)[v] = zero;
-}
-
-// One element: sl[col - c0] += val when col lies in [c0, c0 + w). c0 + w <= cols < 2^31, so
-// the unsigned difference is under w for exactly those columns, negative ones included.
-__device__ inline void add_elem(uint32_t* sl, uint32_t col, uint32_t val, uint32_t c0, uint32_t w) {
-    const uint32_t c = col - c0;
-    if (c < w) (void)__hip_atomic_fetch_add(sl + c, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// Occurrence j's per_occ elements: pairs by 8-byte loads, an odd last one alone.
-__device__ inline void add_occ(uint32_t* sl, const ElemsP& a, uint32_t j, uint32_t c0, uint32_t w) {
-    const uint32_t* cp = (const uint32_t*)a.cols + (int64_t)j * a.per;
-    const uint32_t* vp = (const uint32_t*)a.vals + (int64_t)j * a.per;
-    int e = 0;
-    for (; e + 2 <= a.per; e += 2) {
-        const u32x2 c = ldg8(cp + e), v = ldg8(vp + e);
-        add_elem(sl, c.x, v.x, c0, w);
-        add_elem(sl, c.y, v.y, c0, w);
-    }
-    if (e < a.per) add_elem(sl, cp[e], vp[e], c0, w);
-}
-
 // The slice's w dwords to columns [c0, c0 + w) of row / record u, by threads t of nt: whole
 // vectors as 16-byte stores, a ragged last vector's dwords singly. REC: the thread that
 // stores column 0 stores the key in front of it.

@@ -352,6 +352,26 @@ constexpr int kPushWalkCands = 1536, kPushLongCands = 512, kPushCands = kPushWal
 int co_device(const dml_coalescer* c);
 int co_push_planes(dml_coalescer* c, int32_t value_type, int64_t rowbytes, const int64_t* dev_keys, int64_t n,
                    const void* dev_values, const PushSink& sk, void* stream);
+// ---- element push (dml_push_elems.hip; dml_store_push_elems_device) ----
+// The int32 stores' side of an element push: the shard and its checked adds' verdicts. `cell`
+// takes the call's first negative counter (row-major shard element index, by atomicMin) and
+// `bad` its lowest refused distinct-key index; k_pe_verdict folds the one that comes first in
+// record order into the sticky `neg` or `fver` and resets both. A closed `neg` or `fver` turns
+// the call's kernels into no-ops.
+struct ElemSink {
+    int32_t* data;  // rows x cols
+    int64_t first, last;
+    int32_t cols;   // 1: an IntArrayStore
+    unsigned long long* cell;
+    unsigned long long* bad;
+    unsigned long long* neg;
+    FetchVerdict* fver;
+    hipStream_t apply;
+};
+// dml_coalesce.hip: co_push_planes' stages with the element sum's inputs; `dev_cols` null: every
+// element lands on the key's one counter (cols == 1). Arguments checked by the caller.
+int co_push_elems(dml_coalescer* c, const int64_t* dev_keys, int64_t n, int32_t per_occ, const int32_t* dev_cols,
+                  const int32_t* dev_vals, const ElemSink& sk, void* stream);
 // k_maxdelta_elems alone (dml_moments.hip): n element-index candidates against the running record.
 hipError_t launch_maxdelta_elems(const DeltaCand* cand, int64_t n, MaxDelta* md, int64_t first, int32_t cols,
                                  hipStream_t st);

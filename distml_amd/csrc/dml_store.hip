@@ -682,8 +682,9 @@ int dml::detail::collect_apply_check(dml_store* s, bool block) {
     unsigned long long idx;
     if (int rc = s->neg.poll(block, &idx)) return rc;
     if (idx == kNoPos) return DML_OK;
+    // an IntArrayStore's counter has no column (IntArrayStore.java; its pushes report -1 too)
     return record_error(s, DML_E_NEGATIVE_COUNTER, s->first + (int64_t)(idx / (unsigned long long)s->cols),
-                        (int32_t)(idx % (unsigned long long)s->cols));
+                        s->is_matrix ? (int32_t)(idx % (unsigned long long)s->cols) : -1);
 }
 
 int dml::detail::begin_call(dml_store* s) {
@@ -837,6 +838,7 @@ void dml_store_destroy(dml_store* s) {
         s->crec.destroy();
         s->fver.destroy();
         (void)hipFree(s->fbad_dev);
+        (void)hipFree(s->pe_cell);
         (void)hipFree(s->dstage);
         if (s->hstage) (void)hipHostFree(s->hstage);
         (void)hipFree(s->dscr);

@@ -170,6 +170,9 @@ struct dml_store {
     // int32 owner apply (dml_store_apply_dense_device): index of the first negative final
     // counter, posted behind every checked apply
     dml::detail::Mirror<unsigned long long> neg;
+    // element pushes (dml_store_push_elems_device) fold their first negative counter into `neg`
+    // too; this is the running call's, reset by its verdict kernel
+    unsigned long long* pe_cell = nullptr;
     // timing of the dominant kernel
     const char* kname = nullptr;  // its instantiation, as last launched (dml_store_kernel_name)
     bool timing = false;

@@ -148,6 +148,60 @@ int dml_store_push_planes_device(dml_store* s, dml_coalescer* c, const int64_t* 
     return collect_fetch_check(s, true);
 }
 
+// The element push (dml_push_elems.hip): the plane push's refusals, entry and
+// streams, with the int32 stores' checked adds as the sink (dml::co_push_elems).
+int dml_store_push_elems_device(dml_store* s, dml_coalescer* c, const int64_t* dev_keys, int64_t n, int32_t per_occ,
+                                const int32_t* dev_cols, const int32_t* dev_vals, void* stream) {
+    if (int rc = check_store(s)) return rc;
+    if (!c) return set_err(DML_E_INVALID_ARG, "null coalescer");
+    Entry in(s);
+    if (n < 0) return set_err(DML_E_INVALID_ARG, "negative occurrence count");
+    if (n > 0x7FFFFFFFll) return set_err(DML_E_INVALID_ARG, "lists of 2^31 occurrences and more");
+    if (per_occ < 1 || per_occ > DML_COALESCE_ELEMS_MAX_PER_OCC)
+        return set_err(DML_E_INVALID_ARG, "per_occ outside 1 .. DML_COALESCE_ELEMS_MAX_PER_OCC");
+    if (((uintptr_t)dev_keys & 7) != 0) return set_err(DML_E_INVALID_ARG, "push keys are not 8-byte aligned");
+    if ((((uintptr_t)dev_cols | (uintptr_t)dev_vals) & 3) != 0)
+        return set_err(DML_E_INVALID_ARG, "columns or values are not 4-byte aligned");
+    if (co_device(c) != s->device) return set_err(DML_E_INVALID_ARG, "the coalescer belongs to another device");
+    if (vtype_of(s->desc) != kI32 || s->adagrad)
+        return set_err(DML_E_UNSUPPORTED, "element updates are int32 only: float sums depend on their order");
+    if (s->is_matrix && !s->desc.dense_column)
+        return set_err(DML_E_UNSUPPORTED, "sparse-column matrix rows are not supported (SURVEY defect 3)");
+    if (!s->is_matrix && dev_cols) return set_err(DML_E_INVALID_ARG, "an array store's elements have no column");
+    if (n > 0 && (!dev_keys || !dev_vals || (s->is_matrix && !dev_cols)))
+        return set_err(DML_E_INVALID_ARG, "null keys, columns or values");
+    if (int rc = retire_all(s)) return rc;
+    if (int rc = collect_apply_check(s, false)) return rc;
+    if (int rc = failed(s)) return rc;
+    if (n == 0) return DML_OK;
+    if (!s->fbad_dev) {  // as a device fetch's
+        HIPCHK(hipMalloc((void**)&s->fbad_dev, sizeof(unsigned long long)));
+        HIPCHK(hipMemsetAsync(s->fbad_dev, 0xFF, sizeof(unsigned long long), s->stream));
+    }
+    if (!s->pe_cell) {
+        HIPCHK(hipMalloc((void**)&s->pe_cell, sizeof(unsigned long long)));
+        HIPCHK(hipMemsetAsync(s->pe_cell, 0xFF, sizeof(unsigned long long), s->stream));
+    }
+    if (int rc = s->fver.ensure(s->stream)) return rc;
+    if (int rc = s->neg.ensure(s->stream)) return rc;
+    ElemSink sk{};
+    sk.data = (int32_t*)s->data;
+    sk.first = s->first;
+    sk.last = s->last;
+    sk.cols = s->is_matrix ? s->cols : 1;
+    sk.cell = s->pe_cell;
+    sk.bad = s->fbad_dev;
+    sk.neg = s->neg.dev;
+    sk.fver = s->fver.dev;
+    sk.apply = s->stream;
+    if (int rc = co_push_elems(c, dev_keys, n, per_occ, dev_cols, dev_vals, sk, stream)) return rc;
+    if (int rc = s->fver.post(s->stream)) return rc;
+    if (int rc = s->neg.post(s->stream)) return rc;
+    if (stream) return DML_OK;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return collect_apply_check(s, true);
+}
+
 int dml_store_assign_dense_device(dml_store* s, const void* dev_src, int64_t elems) {
     if (int rc = check_store(s)) return rc;
     Entry in(s);

@@ -361,6 +361,26 @@ class DataStore:
         check(_lib.load().dml_store_push_planes_device(self._h, coalescer._h, C.c_void_p(rows.ptr or None), rows.n,
                                                        C.c_void_p(values_ptr or None), C.c_void_p(stream or None)), self)
 
+    def handlePushElemsDevice(self, format: DataDesc, coalescer: "Coalescer", rows: DeviceKeys, cols_ptr: Optional[int],
+                              vals_ptr: int, per_occ: int, stream: Optional[int] = None) -> None:
+        """LightLDA's element updates straight into an int32 store (dml_store_push_elems_device):
+        what pushDevice of coalescer.run_elems(..., records=True) leaves, with no record in
+        between. `rows` are the occurrence keys and occurrence j holds `per_occ` (column, delta)
+        pairs in the int32[n][per_occ] planes at `cols_ptr` and `vals_ptr` (4-byte aligned). Per
+        distinct key the deltas are summed mod 2^32 per column and the row takes the store's checked
+        add; the first negative counter closes the store with IllegalStateException as a record
+        push would, with the adds up to and including it applied and none after it. IntMatrixStore,
+        and IntArrayStore with cols_ptr None (every element lands on the key's counter); other
+        stores raise. `coalescer` and `stream` as in handlePushPlanesDevice."""
+        self._check_format(format)
+        if not isinstance(rows, DeviceKeys):
+            raise TypeError("handlePushElemsDevice takes DeviceKeys")
+        if not isinstance(coalescer, Coalescer):
+            raise TypeError("handlePushElemsDevice takes a Coalescer")
+        check(_lib.load().dml_store_push_elems_device(self._h, coalescer._h, C.c_void_p(rows.ptr or None), rows.n,
+                                                      per_occ, C.c_void_p(cols_ptr or None), C.c_void_p(vals_ptr or None),
+                                                      C.c_void_p(stream or None)), self)
+
     def writeAll(self, os=None) -> bytes:
         """Big-endian row-major dump (FloatMatrixStore.java:74-81); writes to `os` if given."""
         n = self._rows * self._cols * np.dtype(self.dtype).itemsize

@@ -381,6 +381,50 @@ struct dml_coalescer;
 int dml_store_push_planes_device(dml_store* s, struct dml_coalescer* c, const int64_t* dev_keys, int64_t n,
                                  const void* dev_values, void* stream);
 
+/* LightLDA's element updates straight into an int32 store on its own device: the push a plane
+ * push refuses (no JNI binding, for the same reason). The inputs are dml_coalesce_elems_device's:
+ * dev_keys int64[n], 8-byte aligned, repeats in any order; dev_cols and dev_vals int32[n][per_occ],
+ * 4-byte aligned, 1 <= per_occ <= DML_COALESCE_ELEMS_MAX_PER_OCC. What the store holds afterwards,
+ * values and error state, is byte for byte what the record route leaves at either key width:
+ * for an IntMatrixStore dml_coalesce_elems_device(..., DML_ELEMS_RECORDS) of the same inputs
+ * followed by dml_store_push_batch_device of those records as one push; for an IntArrayStore
+ * dml_coalesce_device at cols = 1 of the per-occurrence sums, dml_records_pack_device and the push.
+ * No record and no update row is ever written (dml_push_elems.hip).
+ *
+ * Per distinct key, ascending, one update row u[c] = sum of the key's vals on column c mod 2^32
+ * is formed; an element whose column lies outside [0, cols) adds nothing and its key is still
+ * listed. The shard row then gets row[c] += u[c] (wrapping) for EVERY column c, and every
+ * result is checked, those with u[c] == 0 included (IntMatrixStore.java:171-178): a negative
+ * counter left by read_all, sync_from or assign fails a listed row with a zero update. A row no
+ * key lists is neither read nor written. Inside one call every (row, column) gets exactly one
+ * add, so the reference's first failing position is the smallest row-major element index whose
+ * result is negative: the shard then holds every add up to and including that one and none
+ * after it, and the store closes with (DML_E_NEGATIVE_COUNTER, key, col) until
+ * dml_store_clear_error (an IntArrayStore: col -1). A counter that dips below zero inside a
+ * key's list and ends >= 0 does not fail: the coalesced sum is what is added, as on the record
+ * route. An element call queued behind an unreported closed verdict applies nothing.
+ *
+ * IntArrayStore: every element of an occurrence lands on the key's one counter and dev_cols
+ * must be NULL (non-null: DML_E_INVALID_ARG). Every store but IntMatrixStore (dense column) and
+ * IntArrayStore is DML_E_UNSUPPORTED; float element updates stay refused because their sums
+ * depend on the order of the adds.
+ *
+ * c, the declared key range, long_min, one call in flight per coalescer, entry, the meaning of
+ * `stream`, the ordering against later pushes and fetches with no flush, stream == NULL making
+ * the call synchronous and the call then returning its own error: all are
+ * dml_store_push_planes_device's. So is the key check (64-bit compare, never an address, the
+ * 4-byte-key difference): the smallest key below first applies nothing, a key above last applies
+ * every in-shard key, and either ends in DML_E_KEY_OUT_OF_SHARD with the lowest bad key and col
+ * -1, unless an in-shard add of the same call went negative: the reference never reaches the
+ * bad record then, and the negative counter is the one error reported.
+ *
+ * DML_E_INVALID_ARG, before anything is launched and with no state changed: a null s or c;
+ * n < 0 or n >= 2^31; per_occ out of range; a null or misaligned input with n > 0; a coalescer
+ * of another device. DML_E_UNSUPPORTED is raised at the same point. n == 0 returns DML_OK with
+ * nothing launched. */
+int dml_store_push_elems_device(dml_store* s, struct dml_coalescer* c, const int64_t* dev_keys, int64_t n,
+                                int32_t per_occ, const int32_t* dev_cols, const int32_t* dev_vals, void* stream);
+
 /* writeAll/readAll (FloatMatrixStore.java:74-91 etc.): big-endian row-major
  * values, the bytes DataOutputStream.writeFloat/writeInt/writeDouble emit.
  * read_all assigns the elements the stream holds before failing with
