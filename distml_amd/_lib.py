@@ -83,6 +83,7 @@ SIGNATURES = {
     "dml_store_fetch_planes_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "dml_store_push_planes_device": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "dml_store_push_elems_device": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "dml_store_push_compact_rows_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dml_store_write_all": (C.c_int, [_vp, _vp, _i64, _P(_i64)]),
     "dml_store_read_all": (C.c_int, [_vp, _vp, _i64]),
     "dml_store_sync_to": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _P(_i64)]),
@@ -129,6 +130,9 @@ SIGNATURES = {
                                            _P(_i64), _P(_i64), _vp]),
     "dml_coalesce_elems_device": (C.c_int, [_vp, _P(dml_desc), _i32, _u32, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64,
                                             _vp, _vp, _P(_i64), _P(_i64), _vp]),
+    "dml_coalesce_elems_compact_device": (C.c_int, [_vp, _P(dml_desc), _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
+                                                    _vp, _i64, _i64, _vp, _P(_i64), _P(_i64), _vp]),
+    "dml_compact_rows_split": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "dml_diag_coalesce_times": (C.c_int, [_vp, _P(C.c_float)]),
     "dml_coalescer_set_long_min": (C.c_int, [_vp, _i64]),
     "dml_diag_coalesce_route": (C.c_int, [_vp, _P(_i64)]),
@@ -219,6 +223,10 @@ DML_ELEMS_ROWS = 0
 DML_ELEMS_RECORDS = 1
 DML_COALESCE_ELEMS_MAX_PER_OCC = 16
 DML_COALESCE_ELEMS_SLICE = 1024
+# ... and compact update rows: the entries from which dml_store_push_compact_rows_device gives a
+# key a block, and the most owners of dml_compact_rows_split
+DML_COMPACT_ROWS_LONG_ENTRIES = 1024
+DML_COMPACT_ROWS_MAX_WORLD = 1024
 
 
 class NativeLibraryMissing(RuntimeError):

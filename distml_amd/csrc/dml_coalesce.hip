@@ -34,6 +34,8 @@
 // hands the sum to dml_push_planes.hip, whose kernels apply it to a store's shard (PushSink).
 // dml::co_push_elems (dml_store_push_elems_device) does the same for element updates into an
 // int32 store's checked adds (dml_push_elems.hip, ElemSink).
+// dml_coalesce_elems_compact_device ends in dml_compact_rows.hip's count, scan and writing passes
+// instead: compact update rows.
 //
 // A segment of the context's long_min occurrences and more is left out by both walks and
 // summed by dml_coalesce_long.hip's kernels instead: the same adds in the same order.
@@ -331,6 +333,8 @@ struct dml_coalescer {
     size_t ws_bytes = 0;
     uint32_t* count_dev = nullptr;  // k_co_offsets' total
     uint32_t* count_host = nullptr; // ... copied here (pinned); the one word the host waits for
+    uint8_t* cr = nullptr;          // compact rows: the non-zero counts per (key, slice), grown on demand
+    size_t cr_bytes = 0;
     hipEvent_t done = nullptr;      // the last call's last kernel
     hipEvent_t handoff = nullptr;   // plane push: the caller's stream, where the store's apply stream takes over
     bool in_flight = false;
@@ -372,6 +376,7 @@ extern "C" void dml_coalescer_destroy(dml_coalescer* c) {
     DeviceGuard g(c->device);
     if (c->in_flight) (void)hipEventSynchronize(c->done);
     if (c->ws) (void)hipFree(c->ws);
+    if (c->cr) (void)hipFree(c->cr);
     if (c->count_dev) (void)hipFree(c->count_dev);
     if (c->count_host) (void)hipHostFree(c->count_host);
     if (c->done) (void)hipEventDestroy(c->done);
@@ -392,6 +397,12 @@ struct CoOut {
     int64_t rec_bytes;   // 0: dense; else the bytes of one push record
     int32_t kdw, pad;
     int64_t* out_len;    // record form: m x rec_bytes; dense form, when given: m x rowbytes
+    // the compact form (dml_coalesce_elems_compact_device): ptr non-null, values_out null, cap in rows
+    int32_t* ptr;
+    int32_t* ecol;
+    int32_t* eval;
+    int64_t cap_entries;
+    int64_t* out_entries;
 };
 
 // The third sum mode's input (dml_coalesce_elems_device): element updates instead of rows.
@@ -567,6 +578,60 @@ extern "C" int dml_coalesce_elems_device(dml_coalescer* c, const dml_desc* desc,
     return co_run(c, d, rowbytes, dev_keys, n, nullptr, &el, o, out_rows, stream);
 }
 
+extern "C" int dml_coalesce_elems_compact_device(dml_coalescer* c, const dml_desc* desc, int32_t cols,
+                                                 const int64_t* dev_keys, int64_t n, int32_t per_occ,
+                                                 const int32_t* dev_cols, const int32_t* dev_vals,
+                                                 int64_t* dev_keys_out, int32_t* dev_ptr_out, int32_t* dev_ecol_out,
+                                                 int32_t* dev_eval_out, int64_t cap_rows, int64_t cap_entries,
+                                                 int32_t* dev_inverse_out, int64_t* out_rows, int64_t* out_entries,
+                                                 void* stream) {
+    // ---- argument checks, the element call's: no HIP call before they pass
+    if (!c || !desc || !out_rows) return set_error(DML_E_INVALID_ARG, "null coalescer, desc or out_rows");
+    if (int rc = dml_record_bytes(desc, cols, 0, nullptr, nullptr)) return rc;  // desc, cols
+    const dml_desc d = *desc;
+    if (d.data_type != DML_DATA_TYPE_MATRIX)
+        return set_error(DML_E_UNSUPPORTED, "compact rows are matrix rows: an array's update is one value per key");
+    if (d.value_type != DML_ELEMENT_TYPE_INT || d.ada_grad)
+        return set_error(DML_E_UNSUPPORTED, "element updates are int32 only: float sums depend on their order");
+    if (per_occ < 1 || per_occ > DML_COALESCE_ELEMS_MAX_PER_OCC)
+        return set_error(DML_E_INVALID_ARG, "per_occ outside 1 .. DML_COALESCE_ELEMS_MAX_PER_OCC");
+    if (n < 0) return set_error(DML_E_INVALID_ARG, "negative occurrence count");
+    if (n * per_occ > 0x7FFFFFFFll) return set_error(DML_E_UNSUPPORTED, "lists of 2^31 elements and more: ptr is int32");
+    if ((((uintptr_t)dev_keys | (uintptr_t)dev_keys_out) & 7u) != 0)
+        return set_error(DML_E_INVALID_ARG, "key array is not 8-byte aligned");
+    if ((((uintptr_t)dev_cols | (uintptr_t)dev_vals | (uintptr_t)dev_ptr_out | (uintptr_t)dev_ecol_out |
+          (uintptr_t)dev_eval_out | (uintptr_t)dev_inverse_out) & 3u) != 0)
+        return set_error(DML_E_INVALID_ARG, "columns, values, ptr, entries or inverse pointer is not 4-byte aligned");
+    if (n > 0 && (!dev_keys || !dev_cols || !dev_vals || !dev_keys_out || !dev_ptr_out || !dev_ecol_out || !dev_eval_out))
+        return set_error(DML_E_INVALID_ARG, "null keys, columns, values or output pointer");
+    {
+        // no output extends past min(n, cap_rows) rows (+ 1 for ptr) or min(n x per_occ, cap_entries) entries
+        const int64_t mmax = cap_rows < 0 ? 0 : std::min(n, cap_rows);
+        const int64_t emax = cap_entries < 0 ? 0 : std::min(n * per_occ, cap_entries);
+        const void* in[3] = {dev_keys, dev_cols, dev_vals};
+        const int64_t inlen[3] = {n * 8, n * per_occ * 4, n * per_occ * 4};
+        const void* outp[5] = {dev_keys_out, dev_ptr_out, dev_ecol_out, dev_eval_out, dev_inverse_out};
+        const int64_t outlen[5] = {mmax * 8, n > 0 ? (mmax + 1) * 4 : 0, emax * 4, emax * 4, dev_inverse_out ? n * 4 : 0};
+        for (int o = 0; o < 5; ++o) {
+            for (int i = 0; i < 3; ++i)
+                if (overlap(outp[o], outlen[o], in[i], inlen[i]))
+                    return set_error(DML_E_INVALID_ARG, "coalesce output overlaps an input");
+            for (int p = o + 1; p < 5; ++p)
+                if (overlap(outp[o], outlen[o], outp[p], outlen[p]))
+                    return set_error(DML_E_INVALID_ARG, "coalesce outputs overlap");
+        }
+    }
+    if (n == 0) {  // an empty list has no ptr either: nothing is written
+        *out_rows = 0;
+        if (out_entries) *out_entries = 0;
+        return DML_OK;
+    }
+    const CoElems el = {dev_cols, dev_vals, cols, per_occ};
+    const CoOut o = {dev_keys_out, nullptr, dev_inverse_out, cap_rows, 0, 0, 0, nullptr,
+                     dev_ptr_out, dev_ecol_out, dev_eval_out, cap_entries, out_entries};
+    return co_run(c, d, 4 * (int64_t)cols, dev_keys, n, nullptr, &el, o, out_rows, stream);
+}
+
 namespace {
 
 // The device side of the three calls, after their argument checks. The sum is dense or
@@ -668,6 +733,28 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
         if (o.out_len) *o.out_len = m * rowbytes;
         if (m > o.cap) return set_error(DML_E_CAPACITY, "more distinct keys than cap_rows");
     }
+    int64_t nitem = 0;
+    if (o.ptr) {
+        // nnz is known only on the device, and this call waits once. So cap_entries is held to the
+        // bound the host does know, nnz <= min(n x per_occ, m x cols): a capacity under it is refused
+        // here, before any write, whatever nnz turns out to be, and one at or above it cannot be short.
+        const int64_t bound = std::min(n * el->per, m > INT64_MAX / el->ncols ? INT64_MAX : m * el->ncols);
+        if (o.cap_entries < bound)
+            return set_error(DML_E_CAPACITY, "cap_entries is under min(n x per_occ, m x cols), the bound on the entries");
+        nitem = m * co_elems_slices(el->ncols);
+        if (nitem > 0x7FFFFFFFll) return set_error(DML_E_UNSUPPORTED, "2^31 (key, slice) items and more");
+        const size_t need_cr = ((size_t)nitem + 1) * 4;
+        if (need_cr > c->cr_bytes) {  // the per-item counts; grown here because m was not known before
+            if (c->cr) (void)hipFree(c->cr);
+            c->cr = nullptr;
+            c->cr_bytes = 0;
+            if (hipMalloc((void**)&c->cr, need_cr + need_cr / 4) != hipSuccess) {
+                (void)hipGetLastError();
+                return set_error(DML_E_NOMEM, "coalescer compact-row counts");
+            }
+            c->cr_bytes = need_cr + need_cr / 4;
+        }
+    }
     int64_t* keys_out = o.keys_out ? o.keys_out : (int64_t*)(c->ws + o_uk);
 
     HIPCHK(hipEventRecord(c->ev[3], st));
@@ -700,6 +787,33 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
         }
         HIPCHK(launch_push_elems(a, nlong > 0, apply));
         HIPCHK(hipEventRecord(c->ev[5], apply));
+        c->timed_sum = true;
+    } else if (el && o.ptr) {
+        CompactP a;
+        a.e.cols = el->cols;
+        a.e.vals = el->vals;
+        a.e.idx = vout;
+        a.e.seg = seg;
+        a.e.out = nullptr;
+        a.e.n = n;
+        a.e.m = m;
+        a.e.rowbytes = rowbytes;
+        a.e.nslice = co_elems_slices(el->ncols);
+        a.e.ncols = el->ncols;
+        a.e.per = el->per;
+        a.e.lmin = lmin;
+        a.e.list = (uint32_t*)(c->ws + o_list);
+        a.e.route = c->count_dev + kRouteWord;
+        a.e.rec = RecP{};
+        a.ptr = o.ptr;
+        a.ecol = o.ecol;
+        a.eval = o.eval;
+        a.cnt = (uint32_t*)c->cr;
+        co_launch_compact(a, nlong > 0, st);
+        HIPCHK(hipGetLastError());
+        if (o.out_entries)  // ptr[m], behind the writing pass; read after the wait on `done` below
+            HIPCHK(hipMemcpyAsync(c->count_host + 2, o.ptr + m, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipEventRecord(c->ev[5], st));
         c->timed_sum = true;
     } else if (el) {
         ElemsP a;
@@ -799,6 +913,11 @@ int co_run(dml_coalescer* c, const dml_desc& d, int64_t rowbytes, const int64_t*
     if (!st) {
         HIPCHK(hipStreamSynchronize(st));
         c->in_flight = false;
+    }
+    if (o.out_entries) {  // the compact form's second wait: for the whole call, whose last copy this is
+        HIPCHK(hipEventSynchronize(c->done));
+        c->in_flight = false;
+        *o.out_entries = (int64_t)c->count_host[2];
     }
     return DML_OK;
 }

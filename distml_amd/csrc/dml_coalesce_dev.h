@@ -163,6 +163,73 @@ __device__ inline void add_occ(uint32_t* sl, const ElemsP& a, uint32_t j, uint32
     if (e < a.per) add_elem(sl, cp[e], vp[e], c0, w);
 }
 
+// ---- an int32 shard slice under the checked add, shared by the element push (dml_push_elems.hip)
+// and the compact-row push (dml_compact_rows.hip) ----
+constexpr uint32_t kPeNone = 0xFFFFFFFFu;
+
+__device__ inline void stg32(void* p, uint32_t v) { *(DML_GLOBAL uint32_t*)p = v; }
+
+// The wave's lowest `c` (kPeNone: none) as every lane's value.
+__device__ inline uint32_t wave_min(uint32_t c) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) c = min(c, (uint32_t)__shfl_xor((int)c, d));
+    return c;
+}
+
+// Vector v of a slice of w dwords at `p`: whole vectors by one 16-byte access, the ragged last
+// one's dwords singly.
+__device__ inline u32x4 load_vec(const uint8_t* p, uint32_t v, uint32_t w) {
+    if (4 * v + 4 <= w) return ldg16(p + 16 * v);
+    u32x4 x = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t d = 0; d < 3; ++d)
+        if (4 * v + d < w) x[d] = ldg32(p + 16 * v + 4 * d);
+    return x;
+}
+__device__ inline void store_vec(uint8_t* p, uint32_t v, uint32_t w, u32x4 x) {
+    if (4 * v + 4 <= w) {
+        stg16(p + 16 * v, x);
+        return;
+    }
+#pragma unroll
+    for (uint32_t d = 0; d < 3; ++d)
+        if (4 * v + d < w) stg32(p + 16 * v + 4 * d, x[d]);
+}
+
+// Vector v of the item's slice: `sh` is what the shard holds there and `up` the update.
+// Apply: sh + up is stored when the update is nonzero, and the lowest dword of the slice whose
+// result is negative is kept in `low`. UNDO: `up` is taken back from the dwords whose slice
+// position lies above `keep` (the failing element's position in this slice; below zero: all).
+template <bool UNDO>
+__device__ inline void update_vec(uint8_t* p, uint32_t v, uint32_t w, u32x4 sh, u32x4 up, int64_t keep, uint32_t& low) {
+    if (4 * v >= w) return;
+    if constexpr (UNDO) {
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+            if ((int64_t)(4 * v + d) <= keep) up[d] = 0u;
+    }
+    const u32x4 x = UNDO ? sh - up : sh + up;
+    if constexpr (!UNDO) {
+#pragma unroll
+        for (int d = 3; d >= 0; --d)
+            if (4 * v + d < w && (int32_t)x[d] < 0) low = min(low, 4 * v + d);
+    }
+    if ((up.x | up.y | up.z | up.w) != 0u) store_vec(p, v, w, x);
+}
+
+// What an UNDO kernel does with the rows of an item: the failing element (row-major) as (row, col).
+struct Undo {
+    int64_t row;
+    uint32_t col;
+};
+// The slice positions of shard row `row`, columns [c0, c0 + w), that stay as applied: all (w - 1
+// and more) when nothing of the slice is taken back, -1 when everything is.
+__device__ inline int64_t undo_keep(const Undo& f, int32_t row, uint32_t c0, uint32_t w) {
+    if (row < f.row) return (int64_t)w;
+    if (row > f.row) return -1;
+    return (int64_t)f.col - (int64_t)c0;
+}
+
 // The order stage for keys declared to lie in [first, first + span), 1 <= span <= 2^32
 // (dml_coalesce_order.hip; dml_coalescer_set_key_range): kout[i] = key ^ sign bit and
 // vout[i] = occurrence index, by key and then by list position, what the library sort leaves.
@@ -214,6 +281,23 @@ struct PushElemsP {
 };
 // has_long: k_co_long_list first. The apply kernels, their undo forms, then the verdict.
 hipError_t launch_push_elems(const PushElemsP& a, bool has_long, hipStream_t st);
+
+// ---- compact update rows (dml_compact_rows.hip) ----
+// The source (dml_coalesce_elems_compact_device): the element sum's inputs in `e` (`e.out` and
+// `e.rec` unused), the three entry arrays, and `cnt`, m x nslice + 1 workspace words: the
+// count pass leaves the non-zeros of item (u, slice) at cnt[u x nslice + slice], the scan turns
+// them into the item's first entry, and the writing pass reads that.
+struct CompactP {
+    ElemsP e;
+    int32_t* ptr;   // int32[m + 1]
+    int32_t* ecol;  // int32[nnz]
+    int32_t* eval;
+    uint32_t* cnt;
+};
+// has_long: k_co_long_list first. Count (long, short), scan, write (long, short).
+void co_launch_compact(const CompactP& a, bool has_long, hipStream_t st);
+
+// The owner's side and the split: PushCompactP, launch_push_compact, launch_compact_split (dml_internal.h).
 
 int co_order_passes(uint64_t span);
 size_t co_order_count_bytes();

@@ -309,6 +309,9 @@ struct FetchVerdict {                // first key outside the shard of the list 
     unsigned long long idx;          // its list index, kNoPos: none
     int64_t key;
 };
+// FetchVerdict::idx of a malformed compact row list (dml_store_push_compact_rows_device; a list
+// index is under 2^31): `key` is then the first key not above its predecessor, -1 for a ptr fault.
+constexpr unsigned long long kVerdictMalformed = kNoPos - 1;
 hipError_t launch_fetch_vec(int vtype, const void* shard, const float* alpha, int32_t cols, const int64_t* keys,
                             int64_t key_lo, int64_t n, int64_t first, int64_t last, uint8_t* out, int64_t rec, int K,
                             int value_slot, unsigned long long* bad, int variant, hipStream_t st);
@@ -372,6 +375,29 @@ struct ElemSink {
 // element lands on the key's one counter (cols == 1). Arguments checked by the caller.
 int co_push_elems(dml_coalescer* c, const int64_t* dev_keys, int64_t n, int32_t per_occ, const int32_t* dev_cols,
                   const int32_t* dev_vals, const ElemSink& sk, void* stream);
+// ---- compact-row push (dml_compact_rows.hip; dml_store_push_compact_rows_device) ----
+// A compact row list into an int32 matrix store's shard. `form` is the call's format cell
+// (kNoPos: well formed; else 2 x the first faulty row index, + 1 when the fault is ptr's),
+// `route` the count of block-route keys and `list` room for m of them; all three are the
+// store's and reset by the call's verdict kernel.
+struct PushCompactP {
+    const int64_t* keys;
+    const int32_t* ptr;
+    const int32_t* ecol;
+    const int32_t* eval;
+    int64_t m;
+    int64_t nslice;
+    int32_t ncols;
+    unsigned long long* form;
+    uint32_t* route;
+    uint32_t* list;
+    ElemSink sink;
+};
+// The check, the applies, their undo forms, then the verdict: all on `st`.
+hipError_t launch_push_compact(const PushCompactP& a, hipStream_t st);
+// dml_compact_rows_split's kernels: row_off / entry_off [world + 1] and the rebased ptr_out[m + world].
+hipError_t launch_compact_split(const int64_t* keys, int64_t m, const int32_t* ptr, int64_t total_rows, int32_t world,
+                                int64_t* row_off, int64_t* entry_off, int32_t* ptr_out, hipStream_t st);
 // k_maxdelta_elems alone (dml_moments.hip): n element-index candidates against the running record.
 hipError_t launch_maxdelta_elems(const DeltaCand* cand, int64_t n, MaxDelta* md, int64_t first, int32_t cols,
                                  hipStream_t st);

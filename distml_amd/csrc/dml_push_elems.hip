@@ -53,11 +53,8 @@ constexpr int kPeVec = kPeSlice / 4 / 64;            // 16-byte vectors of a sli
 constexpr int kPeLongThreads = 1024;
 constexpr int64_t kPeMaxBlocks = (int64_t)1 << 22;
 constexpr int kPeLongMaxBlocks = 2048;
-constexpr uint32_t kPeNone = 0xFFFFFFFFu;
 static_assert(kPeVec * 256 == kPeSlice && kPeWaves * kPeSlice * 4 <= 65536 && kPeSlice / 4 <= kPeLongThreads,
               "a lane holds whole vectors of its slice; a block's slices fit LDS; a long block covers a slice");
-
-__device__ inline void stg32(void* p, uint32_t v) { *(DML_GLOBAL uint32_t*)p = v; }
 
 // Nothing of the call is applied: a sticky verdict is closed, or the list's smallest key lies
 // below the shard. Block-uniform; every kernel of a call reads the same values, because only
@@ -79,66 +76,8 @@ __device__ inline int32_t pe_row(const PushElemsP& a, int64_t u, bool report) {
     return -1;
 }
 
-// The wave's lowest `c` (kPeNone: none) as every lane's value.
-__device__ inline uint32_t wave_min(uint32_t c) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) c = min(c, (uint32_t)__shfl_xor((int)c, d));
-    return c;
-}
-
-// Vector v of a slice of w dwords at `p`: whole vectors by one 16-byte access, the ragged last
-// one's dwords singly.
-__device__ inline u32x4 load_vec(const uint8_t* p, uint32_t v, uint32_t w) {
-    if (4 * v + 4 <= w) return ldg16(p + 16 * v);
-    u32x4 x = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (uint32_t d = 0; d < 3; ++d)
-        if (4 * v + d < w) x[d] = ldg32(p + 16 * v + 4 * d);
-    return x;
-}
-__device__ inline void store_vec(uint8_t* p, uint32_t v, uint32_t w, u32x4 x) {
-    if (4 * v + 4 <= w) {
-        stg16(p + 16 * v, x);
-        return;
-    }
-#pragma unroll
-    for (uint32_t d = 0; d < 3; ++d)
-        if (4 * v + d < w) stg32(p + 16 * v + 4 * d, x[d]);
-}
-
-// Vector v of the item's slice: `sh` is what the shard holds there and `up` the update.
-// Apply: sh + up is stored when the update is nonzero, and the lowest dword of the slice whose
-// result is negative is kept in `low`. UNDO: `up` is taken back from the dwords whose slice
-// position lies above `keep` (the failing element's position in this slice; below zero: all).
-template <bool UNDO>
-__device__ inline void update_vec(uint8_t* p, uint32_t v, uint32_t w, u32x4 sh, u32x4 up, int64_t keep, uint32_t& low) {
-    if (4 * v >= w) return;
-    if constexpr (UNDO) {
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-            if ((int64_t)(4 * v + d) <= keep) up[d] = 0u;
-    }
-    const u32x4 x = UNDO ? sh - up : sh + up;
-    if constexpr (!UNDO) {
-#pragma unroll
-        for (int d = 3; d >= 0; --d)
-            if (4 * v + d < w && (int32_t)x[d] < 0) low = min(low, 4 * v + d);
-    }
-    if ((up.x | up.y | up.z | up.w) != 0u) store_vec(p, v, w, x);
-}
-
-// What an UNDO kernel does with the rows of an item: the failing element (row-major) as (row, col).
-struct Undo {
-    int64_t row;
-    uint32_t col;
-};
-// The slice positions of shard row `row`, columns [c0, c0 + w), that stay as applied: all (w - 1
-// and more) when nothing of the slice is taken back, -1 when everything is.
-__device__ inline int64_t undo_keep(const Undo& f, int32_t row, uint32_t c0, uint32_t w) {
-    if (row < f.row) return (int64_t)w;
-    if (row > f.row) return -1;
-    return (int64_t)f.col - (int64_t)c0;
-}
+// wave_min, load_vec / store_vec, update_vec and undo_keep: dml_coalesce_dev.h, shared with the
+// compact-row push (dml_compact_rows.hip).
 
 template <bool UNDO>
 __global__ __launch_bounds__(kCoBlock) void k_pe_apply(const PushElemsP a) {

@@ -80,7 +80,8 @@ int dml::detail::record_error(dml_store* s, int code, int64_t key, int32_t col) 
     static const char* names[] = {"", "IllegalArgumentException", "ArrayIndexOutOfBoundsException (key outside shard)",
                                   "ArrayIndexOutOfBoundsException (truncated push)", "IllegalStateException (negative counter)"};
     char buf[160];
-    std::snprintf(buf, sizeof buf, "%s: key=%lld col=%d", names[code], (long long)key, col);
+    const char* name = code == DML_E_INVALID_ARG ? "malformed compact row list" : names[code];
+    std::snprintf(buf, sizeof buf, "%s: key=%lld col=%d", name, (long long)key, col);
     return set_err(code, buf);
 }
 
@@ -670,6 +671,8 @@ int dml::detail::collect_fetch_check(dml_store* s, bool block) {
     if (int rc = s->fver.poll(block, &v)) return rc;
     if (v.idx == kNoPos) return DML_OK;
     if (int rc = s->fver.reopen(s->stream)) return rc;
+    // a compact-row push (dml_store_push_compact_rows_device) found its list malformed on the device
+    if (v.idx == kVerdictMalformed) return record_error(s, DML_E_INVALID_ARG, v.key, -1);
     return record_error(s, DML_E_KEY_OUT_OF_SHARD, v.key, -1);
 }
 
@@ -839,6 +842,8 @@ void dml_store_destroy(dml_store* s) {
         s->fver.destroy();
         (void)hipFree(s->fbad_dev);
         (void)hipFree(s->pe_cell);
+        (void)hipFree(s->cr_scratch);
+        if (s->cr_handoff) (void)hipEventDestroy(s->cr_handoff);
         (void)hipFree(s->dstage);
         if (s->hstage) (void)hipHostFree(s->hstage);
         (void)hipFree(s->dscr);

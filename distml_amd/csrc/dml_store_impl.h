@@ -173,6 +173,11 @@ struct dml_store {
     // element pushes (dml_store_push_elems_device) fold their first negative counter into `neg`
     // too; this is the running call's, reset by its verdict kernel
     unsigned long long* pe_cell = nullptr;
+    // compact-row pushes (dml_store_push_compact_rows_device): [format cell | route word | pad |
+    // block-route key list of cr_cap words], grown on demand
+    uint8_t* cr_scratch = nullptr;
+    int64_t cr_cap = 0;
+    hipEvent_t cr_handoff = nullptr;  // the caller's stream, where the apply stream takes over
     // timing of the dominant kernel
     const char* kname = nullptr;  // its instantiation, as last launched (dml_store_kernel_name)
     bool timing = false;

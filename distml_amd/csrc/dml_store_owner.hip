@@ -1,7 +1,8 @@
 // dml_store_owner.hip — what a shard group drives on an owner's store: the applies and
 // commits of slices that arrive in HBM (dml_store_apply_dense_device, dml_store_assign_*_device,
 // dml_store_apply_adagrad_moments_device), the plane push of a worker on the store's own GPU
-// (dml_store_push_planes_device) and the dml::store_* calls of dml_group.hip. Pushes
+// (dml_store_push_planes_device, dml_store_push_elems_device), the compact-row push and split
+// (dml_store_push_compact_rows_device, dml_compact_rows_split) and the dml::store_* calls of dml_group.hip. Pushes
 // before them are retired first; an earlier call's verdict is read only once it has landed.
 #include "dml_store_impl.h"
 
@@ -200,6 +201,105 @@ int dml_store_push_elems_device(dml_store* s, dml_coalescer* c, const int64_t* d
     if (stream) return DML_OK;
     HIPCHK(hipStreamSynchronize(s->stream));
     return collect_apply_check(s, true);
+}
+
+// The compact-row push (dml_compact_rows.hip): the element push's entry, streams
+// and sink, with no coalescer and no host wait: the list arrives ordered and summed, and what is
+// not known about it (its form) is checked on the device.
+int dml_store_push_compact_rows_device(dml_store* s, const int64_t* dev_keys, const int32_t* dev_ptr,
+                                       const int32_t* dev_ecol, const int32_t* dev_eval, int64_t m, void* stream) {
+    if (int rc = check_store(s)) return rc;
+    Entry in(s);
+    if (m < 0) return set_err(DML_E_INVALID_ARG, "negative row count");
+    if (m > 0x7FFFFFFFll) return set_err(DML_E_INVALID_ARG, "lists of 2^31 rows and more");
+    if (((uintptr_t)dev_keys & 7) != 0) return set_err(DML_E_INVALID_ARG, "push keys are not 8-byte aligned");
+    if ((((uintptr_t)dev_ptr | (uintptr_t)dev_ecol | (uintptr_t)dev_eval) & 3) != 0)
+        return set_err(DML_E_INVALID_ARG, "ptr, columns or values are not 4-byte aligned");
+    if (vtype_of(s->desc) != kI32 || s->adagrad || !s->is_matrix)
+        return set_err(DML_E_UNSUPPORTED, "compact rows are IntMatrixStore updates: the record route serves the rest");
+    if (!s->desc.dense_column)
+        return set_err(DML_E_UNSUPPORTED, "sparse-column matrix rows are not supported (SURVEY defect 3)");
+    if (m > 0 && (!dev_keys || !dev_ptr || !dev_ecol || !dev_eval))
+        return set_err(DML_E_INVALID_ARG, "null keys, ptr, columns or values");
+    if (int rc = retire_all(s)) return rc;
+    if (int rc = collect_apply_check(s, false)) return rc;
+    if (int rc = failed(s)) return rc;
+    if (m == 0) return DML_OK;
+    if (!s->fbad_dev) {  // as a device fetch's
+        HIPCHK(hipMalloc((void**)&s->fbad_dev, sizeof(unsigned long long)));
+        HIPCHK(hipMemsetAsync(s->fbad_dev, 0xFF, sizeof(unsigned long long), s->stream));
+    }
+    if (!s->pe_cell) {
+        HIPCHK(hipMalloc((void**)&s->pe_cell, sizeof(unsigned long long)));
+        HIPCHK(hipMemsetAsync(s->pe_cell, 0xFF, sizeof(unsigned long long), s->stream));
+    }
+    if (m > s->cr_cap) {  // only a list longer than every one before it: the kernels of earlier calls end first
+        if (s->cr_scratch) {
+            HIPCHK(hipStreamSynchronize(s->stream));
+            HIPCHK(hipFree(s->cr_scratch));
+        }
+        s->cr_scratch = nullptr;
+        s->cr_cap = 0;
+        const int64_t cap = m + m / 4;
+        HIPCHK(hipMalloc((void**)&s->cr_scratch, 16 + (size_t)cap * 4));
+        HIPCHK(hipMemsetAsync(s->cr_scratch, 0xFF, 8, s->stream));    // the format cell: open
+        HIPCHK(hipMemsetAsync(s->cr_scratch + 8, 0, 8, s->stream));   // the route word
+        s->cr_cap = cap;
+    }
+    if (int rc = s->fver.ensure(s->stream)) return rc;
+    if (int rc = s->neg.ensure(s->stream)) return rc;
+    PushCompactP a{};
+    a.keys = dev_keys;
+    a.ptr = dev_ptr;
+    a.ecol = dev_ecol;
+    a.eval = dev_eval;
+    a.m = m;
+    a.nslice = ((int64_t)s->cols + DML_COALESCE_ELEMS_SLICE - 1) / DML_COALESCE_ELEMS_SLICE;
+    a.ncols = s->cols;
+    a.form = (unsigned long long*)s->cr_scratch;
+    a.route = (uint32_t*)(s->cr_scratch + 8);
+    a.list = (uint32_t*)(s->cr_scratch + 16);
+    a.sink.data = (int32_t*)s->data;
+    a.sink.first = s->first;
+    a.sink.last = s->last;
+    a.sink.cols = s->cols;
+    a.sink.cell = s->pe_cell;
+    a.sink.bad = s->fbad_dev;
+    a.sink.neg = s->neg.dev;
+    a.sink.fver = s->fver.dev;
+    a.sink.apply = s->stream;
+    if (stream && (hipStream_t)stream != s->stream) {  // the list is complete on `stream`: no host wait
+        if (!s->cr_handoff) HIPCHK(hipEventCreateWithFlags(&s->cr_handoff, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(s->cr_handoff, (hipStream_t)stream));
+        HIPCHK(hipStreamWaitEvent(s->stream, s->cr_handoff, 0));
+    }
+    HIPCHK(launch_push_compact(a, s->stream));
+    if (int rc = s->fver.post(s->stream)) return rc;
+    if (int rc = s->neg.post(s->stream)) return rc;
+    if (stream) return DML_OK;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return collect_apply_check(s, true);
+}
+
+int dml_compact_rows_split(const int64_t* dev_keys, int64_t m, const int32_t* dev_ptr, int64_t total_rows,
+                           int32_t world, int64_t* dev_row_off, int64_t* dev_entry_off, int32_t* dev_ptr_out,
+                           void* stream) {
+    if (m < 0 || m > 0x7FFFFFFFll) return set_err(DML_E_INVALID_ARG, "row count outside 0 .. 2^31 - 1");
+    if (total_rows < 1 || world < 1 || world > DML_COMPACT_ROWS_MAX_WORLD)
+        return set_err(DML_E_INVALID_ARG, "total_rows < 1, or world outside 1 .. DML_COMPACT_ROWS_MAX_WORLD");
+    if (!dev_ptr || !dev_row_off || !dev_entry_off || !dev_ptr_out || (m > 0 && !dev_keys))
+        return set_err(DML_E_INVALID_ARG, "null keys, ptr or output pointer");
+    if ((((uintptr_t)dev_keys | (uintptr_t)dev_row_off | (uintptr_t)dev_entry_off) & 7) != 0)
+        return set_err(DML_E_INVALID_ARG, "keys or offsets are not 8-byte aligned");
+    if ((((uintptr_t)dev_ptr | (uintptr_t)dev_ptr_out) & 3) != 0)
+        return set_err(DML_E_INVALID_ARG, "ptr arrays are not 4-byte aligned");
+    hipPointerAttribute_t at{};  // the kernels run where the list lies
+    HIPCHK(hipPointerGetAttributes(&at, dev_ptr));
+    DeviceGuard g(at.device);
+    HIPCHK(launch_compact_split(dev_keys, m, dev_ptr, total_rows, world, dev_row_off, dev_entry_off, dev_ptr_out,
+                                (hipStream_t)stream));
+    if (!stream) HIPCHK(hipStreamSynchronize(nullptr));
+    return DML_OK;
 }
 
 int dml_store_assign_dense_device(dml_store* s, const void* dev_src, int64_t elems) {

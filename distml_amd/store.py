@@ -381,6 +381,24 @@ class DataStore:
                                                       per_occ, C.c_void_p(cols_ptr or None), C.c_void_p(vals_ptr or None),
                                                       C.c_void_p(stream or None)), self)
 
+    def handlePushCompactRowsDevice(self, format: DataDesc, rows: DeviceKeys, ptr_ptr: int, ecol_ptr: int,
+                                    eval_ptr: int, stream: Optional[int] = None) -> None:
+        """A compact row list (Coalescer.run_elems_compact, or an owner's run of one after
+        compact_rows_split) straight into an IntMatrixStore (dml_store_push_compact_rows_device):
+        what one record push of the dense rows leaves, values and error state. `rows` are the m
+        distinct keys, strictly ascending; `ptr_ptr` the int32[m + 1] entry ranges, `ecol_ptr` and
+        `eval_ptr` the int32 (column, value) entries. Every column of a listed row takes the
+        store's checked add, an empty range included. No coalescer, no sort and no host wait: the
+        list's form is checked on the device, and a malformed one applies nothing and closes the
+        store with code DML_E_INVALID_ARG. `stream` as in handlePushElemsDevice."""
+        self._check_format(format)
+        if not isinstance(rows, DeviceKeys):
+            raise TypeError("handlePushCompactRowsDevice takes DeviceKeys")
+        check(_lib.load().dml_store_push_compact_rows_device(self._h, C.c_void_p(rows.ptr or None),
+                                                             C.c_void_p(ptr_ptr or None), C.c_void_p(ecol_ptr or None),
+                                                             C.c_void_p(eval_ptr or None), rows.n,
+                                                             C.c_void_p(stream or None)), self)
+
     def writeAll(self, os=None) -> bytes:
         """Big-endian row-major dump (FloatMatrixStore.java:74-81); writes to `os` if given."""
         n = self._rows * self._cols * np.dtype(self.dtype).itemsize
@@ -672,6 +690,19 @@ def expand_fetch_device(format: DataDesc, cols: int, records_ptr: int, m: int, i
                                                 C.c_void_p(stream or None)))
 
 
+def compact_rows_split(keys: DeviceKeys, ptr_ptr: int, total_rows: int, world: int, row_off_ptr: int,
+                       entry_off_ptr: int, ptr_out_ptr: int, stream: Optional[int] = None) -> None:
+    """A compact row list cut into the runs of KeyRange(0, total_rows - 1).linearSplit(world):
+    int64[world + 1] row and entry offsets at `row_off_ptr` / `entry_off_ptr`, and every owner's
+    ptr slice rebased to 0 at `ptr_out_ptr` (int32[keys.n + world]; owner q's starts at word
+    row_off[q] + q). Keys below 0 or at and above total_rows fall in no run
+    (dml_compact_rows_split)."""
+    check(_lib.load().dml_compact_rows_split(C.c_void_p(keys.ptr or None), int(keys.n), C.c_void_p(ptr_ptr or None),
+                                             int(total_rows), int(world), C.c_void_p(row_off_ptr or None),
+                                             C.c_void_p(entry_off_ptr or None), C.c_void_p(ptr_out_ptr or None),
+                                             C.c_void_p(stream or None)))
+
+
 # ---- the worker's KeyList + HashMap accumulate on the device (dml_coalesce_device) --------
 class Coalescer:
     """A coalescer context (dml_coalescer): workspace, a pinned count word and one event on
@@ -746,6 +777,28 @@ class Coalescer:
                                                     C.c_void_p(keys_out_ptr or None), C.c_void_p(inverse_ptr or None),
                                                     C.byref(m), C.byref(nbytes), C.c_void_p(stream or None)))
         return m.value, nbytes.value
+
+    def run_elems_compact(self, format: DataDesc, cols: int, keys: DeviceKeys, cols_ptr: int, vals_ptr: int,
+                          per_occ: int, keys_out_ptr: int, ptr_out_ptr: int, ecol_out_ptr: int, eval_out_ptr: int,
+                          cap_rows: int, cap_entries: int, inverse_ptr: Optional[int] = None,
+                          stream: Optional[int] = None, want_entries: bool = False):
+        """run_elems with compact update rows as the output: the distinct keys ascending at
+        `keys_out_ptr` (int64[m]), `ptr_out_ptr` (int32[m + 1]) and per key the non-zero
+        (column, summed delta) entries, columns ascending, at `ecol_out_ptr` / `eval_out_ptr`:
+        8 bytes per touched column instead of a dense row per key. A key whose deltas cancel or
+        miss [0, cols) is listed with no entry. Returns (m, nnz); nnz is None unless
+        `want_entries`, which costs a second host wait (the count otherwise stays on the device
+        as ptr[m]). `cap_entries` must reach min(keys.n * per_occ, m * cols), the bound the host
+        knows; keys.n * per_occ always does. A short capacity raises with code DML_E_CAPACITY
+        and nothing written (dml_coalesce_elems_compact_device)."""
+        m, nnz = C.c_int64(), C.c_int64()
+        check(_lib.load().dml_coalesce_elems_compact_device(
+            self._h, C.byref(format.to_c()), int(cols), C.c_void_p(keys.ptr or None), int(keys.n), int(per_occ),
+            C.c_void_p(cols_ptr or None), C.c_void_p(vals_ptr or None), C.c_void_p(keys_out_ptr or None),
+            C.c_void_p(ptr_out_ptr or None), C.c_void_p(ecol_out_ptr or None), C.c_void_p(eval_out_ptr or None),
+            int(cap_rows), int(cap_entries), C.c_void_p(inverse_ptr or None), C.byref(m),
+            C.byref(nnz) if want_entries else None, C.c_void_p(stream or None)))
+        return m.value, (nnz.value if want_entries else None)
 
     def stage_times(self):
         """(order, heads, sum) HIP-event milliseconds of the last completed run

@@ -425,6 +425,41 @@ int dml_store_push_planes_device(dml_store* s, struct dml_coalescer* c, const in
 int dml_store_push_elems_device(dml_store* s, struct dml_coalescer* c, const int64_t* dev_keys, int64_t n,
                                 int32_t per_occ, const int32_t* dev_cols, const int32_t* dev_vals, void* stream);
 
+/* A compact row list (see dml_coalesce_elems_compact_device) straight into an IntMatrixStore's
+ * shard: the owner's end of the route on which element updates cross ranks. What the store holds
+ * afterwards, values and error state, is byte for byte what one record push of the m dense rows
+ * [key][u] leaves, u[c] = the sum mod 2^32 of the key's entries on column c. The list arrives
+ * ordered and summed, so the call needs no sort, no coalescer and NO HOST WAIT: with a non-null
+ * `stream` it records an event there, makes the apply stream wait for it and enqueues its kernels
+ * (dml_compact_rows.hip).
+ *
+ * Every column of a listed row is added and checked, a zero update and an empty entry range
+ * included; first negative counter, what the shard then holds, the closed store, a call queued
+ * behind a closed verdict, the 64-bit key check and its ordering against a negative counter,
+ * entry, `stream`, ordering against later pushes and fetches with no flush, and stream == NULL
+ * making the call synchronous and returning its own error: all are
+ * dml_store_push_elems_device's.
+ *
+ * The list may come from another rank, so its form is checked on the device before any store:
+ * ptr[0] == 0, ptr non-decreasing, keys strictly ascending. A malformed list applies nothing
+ * and closes the store with (DML_E_INVALID_ARG, the first key that is not above its
+ * predecessor, col -1), the key -1 when the lowest fault is ptr's; it is reported like a key
+ * outside the shard, by the call itself when stream == NULL and by flush() or a later call
+ * otherwise. Entries need not be canonical: repeated and unordered columns of a key sum, and an
+ * entry whose column lies outside [0, cols) adds nothing. ecol and eval must hold ptr[m]
+ * entries; the transport knows that length, this call does not.
+ *
+ * A key with DML_COMPACT_ROWS_LONG_ENTRIES entries and more is applied by a block per row
+ * slice, the others by a wave; the bytes are the same.
+ *
+ * DML_E_INVALID_ARG, before anything is launched and with no state changed: a null s; m < 0 or
+ * m >= 2^31; a null or misaligned array with m > 0. DML_E_UNSUPPORTED, at the same point: every
+ * store but IntMatrixStore with dense columns (IntArrayStore included: the topic totals are a
+ * thousand records and the record route serves them). m == 0: DML_OK, nothing launched. */
+#define DML_COMPACT_ROWS_LONG_ENTRIES 1024
+int dml_store_push_compact_rows_device(dml_store* s, const int64_t* dev_keys, const int32_t* dev_ptr,
+                                       const int32_t* dev_ecol, const int32_t* dev_eval, int64_t m, void* stream);
+
 /* writeAll/readAll (FloatMatrixStore.java:74-91 etc.): big-endian row-major
  * values, the bytes DataOutputStream.writeFloat/writeInt/writeDouble emit.
  * read_all assigns the elements the stream holds before failing with
@@ -968,6 +1003,66 @@ int dml_coalesce_elems_device(dml_coalescer* c, const dml_desc* desc, int32_t co
                               int32_t form, void* dev_out, int64_t cap_bytes,
                               int64_t* dev_keys_out, int32_t* dev_inverse_out,
                               int64_t* out_rows, int64_t* out_len, void* stream);
+/* Compact update rows: the form in which a rank's element updates leave it. A
+ * compact row list for a matrix of `cols` int32 columns is four device arrays, each 4-byte
+ * aligned and keys 8-byte aligned:
+ *   keys  int64[m]      strictly ascending as signed 64-bit values
+ *   ptr   int32[m + 1]  ptr[0] == 0, non-decreasing, ptr[m] == nnz
+ *   ecol  int32[nnz]    the entries of key u are ptr[u] .. ptr[u + 1]
+ *   eval  int32[nnz]
+ * dml_coalesce_elems_compact_device writes the CANONICAL form: a key's columns ascend strictly
+ * and lie in [0, cols), every eval is non-zero and is the sum mod 2^32 of the key's deltas on
+ * that column. A key whose deltas all cancel, or all lie outside [0, cols), is still listed,
+ * with an empty entry range: LightLDA's KeyList holds the word whatever the sampler did, and the
+ * store checks every column of a listed row. The keys and the inverse are byte-equal to
+ * dml_coalesce_elems_device's, and scattering the rows into a zeroed int32[m][cols] plane gives
+ * its DML_ELEMS_ROWS plane. A dense record is 4 x cols bytes per key however few columns its
+ * occurrences touched; a compact row is 8 bytes per touched column and 12 per key.
+ *
+ * Inputs, descs (int32 matrix, dense column; the rest DML_E_UNSUPPORTED), the order stage with a
+ * declared key range, long_min, one call in flight per context, `stream` and the one host wait
+ * for m are dml_coalesce_elems_device's. nnz <= n x per_occ always, and n x per_occ >= 2^31 is
+ * DML_E_UNSUPPORTED (ptr is int32).
+ *
+ * Capacities. cap_rows counts keys (ptr needs cap_rows + 1 words). nnz is known only on the
+ * device and the call waits once, for m, so cap_entries is NOT compared with nnz: after the
+ * wait it must be at least min(n x per_occ, m x cols), the bound on nnz the host knows.
+ * A smaller one is DML_E_CAPACITY even where nnz would have fitted; one at or above the bound
+ * can never be short, so no kernel ever writes past it. DML_E_CAPACITY (either capacity) sets
+ * *out_rows = m and writes NOTHING, the inverse included.
+ *
+ * The entry count stays on the device as ptr[m]. A non-null out_entries returns it: ptr[m] is
+ * then copied to the host behind the writing pass and the call waits a second time, for its
+ * own completion event, so it returns with every output complete.
+ *
+ * DML_E_INVALID_ARG, before any HIP call: a null c, desc or out_rows, n < 0, cols <= 0, per_occ
+ * outside 1..16, a null input or output (the inverse excepted) with n > 0, a misaligned
+ * pointer, an output that overlaps an input or another output. n == 0: DML_OK, *out_rows = 0,
+ * nothing written (no ptr[0] either). */
+int dml_coalesce_elems_compact_device(dml_coalescer* c, const dml_desc* desc, int32_t cols,
+                                      const int64_t* dev_keys, int64_t n, int32_t per_occ,
+                                      const int32_t* dev_cols, const int32_t* dev_vals,
+                                      int64_t* dev_keys_out, int32_t* dev_ptr_out, int32_t* dev_ecol_out,
+                                      int32_t* dev_eval_out, int64_t cap_rows, int64_t cap_entries,
+                                      int32_t* dev_inverse_out, int64_t* out_rows, int64_t* out_entries,
+                                      void* stream);
+/* A compact row list, keys ascending, cut into the runs of the `world` owners of
+ * KeyRange.linearSplit(world) over [0, total_rows): dev_row_off[q] .. dev_row_off[q + 1] are
+ * owner q's rows and dev_entry_off[q] .. dev_entry_off[q + 1] its entries (int64[world + 1]
+ * each, on the device). Keys below 0 lie before dev_row_off[0] and keys at and above total_rows
+ * behind dev_row_off[world]: they belong to no run and are dropped, as in dml_group_pull's
+ * partition. A slice of ptr does not start at 0, so the call also writes every owner's slice
+ * REBASED, into dev_ptr_out (int32[m + world]): owner q's ptr is the rows_q + 1 words at
+ * dev_ptr_out + dev_row_off[q] + q, and (dev_keys + row_off[q], that ptr, dev_ecol +
+ * entry_off[q], dev_eval + entry_off[q], rows_q) is a compact row list of its own, which
+ * dml_store_push_compact_rows_device takes as it is (no ptr_base argument exists). One
+ * binary search per boundary and one pass over ptr, on `stream` (NULL: synchronous); no host
+ * wait. DML_E_INVALID_ARG: m outside 0 .. 2^31 - 1, total_rows < 1, world outside
+ * 1 .. DML_COMPACT_ROWS_MAX_WORLD, a null or misaligned pointer. */
+#define DML_COMPACT_ROWS_MAX_WORLD 1024
+int dml_compact_rows_split(const int64_t* dev_keys, int64_t m, const int32_t* dev_ptr, int64_t total_rows,
+                           int32_t world, int64_t* dev_row_off, int64_t* dev_entry_off, int32_t* dev_ptr_out,
+                           void* stream);
 /* The coalescer's tiling, the sizes its tests place edges at: sorted keys per block of
  * k_co_heads; occurrence indices a group of k_co_sum fetches at a time (a group of fewer
  * lanes fetches one per lane); rows whose loads it issues before the first add. */
