@@ -9,7 +9,8 @@ from .datadesc import ALL, EMPTY, DataDesc, KeyCollection, KeyList, KeyRange  # 
 from .store import (ArrayIndexOutOfBoundsException, Coalescer, DataStore, DeviceBatch, DeviceKeys,  # noqa: F401
                     DistMLException, DMatrix, compact_rows_split,
                     IllegalArgumentException, IllegalStateException, Model, NativeError,
-                    encode_array_push, encode_matrix_push, expand_fetch_device, pack_push_device, pinned_empty,
+                    encode_array_push, encode_matrix_push, expand_compact_rows_device, expand_fetch_device,
+                    pack_push_device, pinned_empty,
                     record_bytes, unpack_fetch_device)
 
 __version__ = "0.1.0"

@@ -84,6 +84,7 @@ SIGNATURES = {
     "dml_store_push_planes_device": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "dml_store_push_elems_device": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "dml_store_push_compact_rows_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "dml_store_fetch_compact_rows_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _P(_i64), _vp]),
     "dml_store_write_all": (C.c_int, [_vp, _vp, _i64, _P(_i64)]),
     "dml_store_read_all": (C.c_int, [_vp, _vp, _i64]),
     "dml_store_sync_to": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _P(_i64)]),
@@ -122,6 +123,7 @@ SIGNATURES = {
     "dml_records_pack_device": (C.c_int, [_P(dml_desc), _i32, _u32, _vp, _i64, _i64, _vp, _vp, _i64, _P(_i64), _vp]),
     "dml_records_unpack_device": (C.c_int, [_P(dml_desc), _i32, _u32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "dml_records_expand_device": (C.c_int, [_P(dml_desc), _i32, _u32, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "dml_compact_rows_expand_device": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
     "dml_diag_codec_knob": (C.c_int, [_i32, _i64]),
     "dml_coalescer_create": (C.c_int, [_i32, _P(_vp)]),
     "dml_coalescer_destroy": (None, [_vp]),

@@ -15,7 +15,8 @@
 //                 wave is one round; the 16 waves' popcounts meet in LDS.
 //   k_cr_scan     one block: cnt[] to its exclusive running sum, 4 counts per thread and tiles of
 //                 4096 carried forward; ptr[u] = the sum in front of key u's first slice,
-//                 ptr[m] = cnt[m x nslice] = nnz.
+//                 ptr[m] = cnt[m x nslice] = nnz. The compact fetch (dml_fetch_compact.hip) runs
+//                 it too, through launch_compact_scan.
 //   k_cr_src<true>, k_cr_src_long<true>   the writing pass. The slice is REBUILT, not kept: kept
 //                 slices are the dense plane (m x 4 x cols bytes written and read back, 262 MB at
 //                 config 5), rebuilt ones cost a second read of the elements (16 MB there). Per
@@ -444,11 +445,15 @@ __global__ __launch_bounds__(kCoBlock) void k_cr_rebase(const int32_t* __restric
 
 }  // namespace
 
+void launch_compact_scan(uint32_t* cnt, int64_t nitem, int64_t nslice, int32_t* ptr, hipStream_t st) {
+    hipLaunchKernelGGL(k_cr_scan, dim3(1), dim3(kCrLongThreads), 0, st, cnt, nitem, nslice, ptr);
+}
+
 void co_launch_compact(const CompactP& a, bool has_long, hipStream_t st) {
     const ElemsP& q = a.e;
     if (has_long) co_launch_long_list(q.seg, q.n, q.m, q.lmin, q.list, q.route, st);
     launch_src<false>(a, has_long, st);
-    hipLaunchKernelGGL(k_cr_scan, dim3(1), dim3(kCrLongThreads), 0, st, a.cnt, q.m * q.nslice, q.nslice, a.ptr);
+    launch_compact_scan(a.cnt, q.m * q.nslice, q.nslice, a.ptr, st);
     launch_src<true>(a, has_long, st);
 }
 

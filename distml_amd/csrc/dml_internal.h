@@ -398,6 +398,28 @@ hipError_t launch_push_compact(const PushCompactP& a, hipStream_t st);
 // dml_compact_rows_split's kernels: row_off / entry_off [world + 1] and the rebased ptr_out[m + world].
 hipError_t launch_compact_split(const int64_t* keys, int64_t m, const int32_t* ptr, int64_t total_rows, int32_t world,
                                 int64_t* row_off, int64_t* entry_off, int32_t* ptr_out, hipStream_t st);
+// k_cr_scan alone (one block): cnt[0 .. nitem) from counts to their exclusive running sum,
+// cnt[nitem] = the total; ptr[u] = cnt[u x nslice], ptr[nitem / nslice] = the total.
+void launch_compact_scan(uint32_t* cnt, int64_t nitem, int64_t nslice, int32_t* ptr, hipStream_t st);
+// ---- compact fetch (dml_fetch_compact.hip; dml_store_fetch_compact_rows_device) ----
+// The rows of keys[0 .. n) of an int32 matrix shard as a compact row list without its keys.
+// `cnt`: n x nslice + 1 words of the store's scratch (the count pass's counts, then the scan's
+// running sum); `bad` takes the lowest refused list index. n x cols < 2^31.
+struct FetchCompactP {
+    const int32_t* data;  // rows x cols
+    const int64_t* keys;  // int64[n]
+    int64_t n, first, last;
+    int64_t nslice;       // slices of DML_COALESCE_ELEMS_SLICE dwords of a row
+    int32_t cols;
+    uint32_t* cnt;
+    int32_t* ptr;         // int32[n + 1], always written whole
+    int32_t* ecol;        // int32[cap], written only when ptr[n] <= cap
+    int32_t* eval;
+    int64_t cap;
+    unsigned long long* bad;
+};
+// The count pass, k_cr_scan, the writing pass: all on `st`.
+hipError_t launch_fetch_compact(const FetchCompactP& a, hipStream_t st);
 // k_maxdelta_elems alone (dml_moments.hip): n element-index candidates against the running record.
 hipError_t launch_maxdelta_elems(const DeltaCand* cand, int64_t n, MaxDelta* md, int64_t first, int32_t cols,
                                  hipStream_t st);

@@ -844,6 +844,8 @@ void dml_store_destroy(dml_store* s) {
         (void)hipFree(s->pe_cell);
         (void)hipFree(s->cr_scratch);
         if (s->cr_handoff) (void)hipEventDestroy(s->cr_handoff);
+        (void)hipFree(s->cf_cnt);
+        if (s->cf_host) (void)hipHostFree(s->cf_host);
         (void)hipFree(s->dstage);
         if (s->hstage) (void)hipHostFree(s->hstage);
         (void)hipFree(s->dscr);

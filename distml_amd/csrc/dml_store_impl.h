@@ -178,6 +178,11 @@ struct dml_store {
     uint8_t* cr_scratch = nullptr;
     int64_t cr_cap = 0;
     hipEvent_t cr_handoff = nullptr;  // the caller's stream, where the apply stream takes over
+    // compact fetches (dml_store_fetch_compact_rows_device): the (key, slice) counts, cf_cap + 1
+    // words grown on demand, and the pinned word a call that wants its entry count reads ptr[n] from
+    uint32_t* cf_cnt = nullptr;
+    int64_t cf_cap = 0;
+    int32_t* cf_host = nullptr;
     // timing of the dominant kernel
     const char* kname = nullptr;  // its instantiation, as last launched (dml_store_kernel_name)
     bool timing = false;

@@ -375,6 +375,87 @@ int dml_store_fetch_planes_device(dml_store* s, const int64_t* dev_keys, int64_t
     return finish_device_fetch(s, dev_keys, (hipStream_t)stream);
 }
 
+// The compact fetch (dml_fetch_compact.hip): the plane fetch's entry, streams and
+// verdict with a compact row list as the output. The entry count exists only on the device: the
+// writing pass holds it against cap_entries there, and only a call that asks for it waits.
+int dml_store_fetch_compact_rows_device(dml_store* s, const int64_t* dev_keys, int64_t n, int32_t* dev_ptr_out,
+                                        int32_t* dev_ecol_out, int32_t* dev_eval_out, int64_t cap_entries,
+                                        int64_t* out_entries, void* stream) {
+    if (int rc = check_store(s)) return rc;
+    Entry in(s);
+    if (n < 0 || n > 0x7FFFFFFFll) return set_err(DML_E_INVALID_ARG, "key count outside 0 .. 2^31 - 1");
+    if (cap_entries < 0) return set_err(DML_E_INVALID_ARG, "negative entry capacity");
+    if (n > 0 && (!dev_keys || !dev_ptr_out)) return set_err(DML_E_INVALID_ARG, "null keys or ptr");
+    if (cap_entries > 0 && (!dev_ecol_out || !dev_eval_out)) return set_err(DML_E_INVALID_ARG, "null entry arrays");
+    if (((uintptr_t)dev_keys & 7) != 0) return set_err(DML_E_INVALID_ARG, "fetch keys are not 8-byte aligned");
+    if ((((uintptr_t)dev_ptr_out | (uintptr_t)dev_ecol_out | (uintptr_t)dev_eval_out) & 3) != 0)
+        return set_err(DML_E_INVALID_ARG, "ptr, columns or values are not 4-byte aligned");
+    {
+        // the entry arrays never extend past min(cap_entries, n x cols) entries
+        const int64_t emax = std::min(cap_entries, n * (int64_t)s->cols) * 4;
+        const void* outp[3] = {dev_ptr_out, dev_ecol_out, dev_eval_out};
+        const int64_t outlen[3] = {n > 0 ? (n + 1) * 4 : 0, emax, emax};
+        for (int o = 0; o < 3; ++o) {
+            if (extents_overlap(outp[o], outlen[o], dev_keys, n * 8))
+                return set_err(DML_E_INVALID_ARG, "compact fetch output overlaps the keys");
+            for (int p = o + 1; p < 3; ++p)
+                if (extents_overlap(outp[o], outlen[o], outp[p], outlen[p]))
+                    return set_err(DML_E_INVALID_ARG, "compact fetch outputs overlap");
+        }
+    }
+    if (vtype_of(s->desc) != kI32 || s->adagrad || !s->is_matrix)
+        return set_err(DML_E_UNSUPPORTED, "compact rows are IntMatrixStore rows: the plane and record fetches serve the rest");
+    if (!s->desc.dense_column)
+        return set_err(DML_E_UNSUPPORTED, "sparse-column matrix rows are not supported (SURVEY defect 3)");
+    if (n * (int64_t)s->cols > 0x7FFFFFFFll)
+        return set_err(DML_E_UNSUPPORTED, "n x cols of 2^31 and more: ptr is int32");
+    if (int rc = begin_call(s)) return rc;
+    if (n == 0) {
+        if (out_entries) *out_entries = 0;
+        return DML_OK;
+    }
+    if (int rc = ensure_fetch_record(s)) return rc;
+    const int64_t nslice = ((int64_t)s->cols + DML_COALESCE_ELEMS_SLICE - 1) / DML_COALESCE_ELEMS_SLICE;
+    const int64_t nitem = n * nslice;
+    if (nitem > s->cf_cap) {  // only a list longer than every one before it: the kernels of earlier calls end first
+        if (s->cf_cnt) {
+            HIPCHK(hipStreamSynchronize(s->stream));
+            HIPCHK(hipFree(s->cf_cnt));
+        }
+        s->cf_cnt = nullptr;
+        s->cf_cap = 0;
+        const int64_t cap = nitem + nitem / 4;
+        HIPCHK(hipMalloc((void**)&s->cf_cnt, ((size_t)cap + 1) * 4));
+        s->cf_cap = cap;
+    }
+    if (out_entries && !s->cf_host) HIPCHK(hipHostMalloc((void**)&s->cf_host, sizeof(int32_t), hipHostMallocDefault));
+    FetchCompactP a{};
+    a.data = (const int32_t*)s->data;
+    a.keys = dev_keys;
+    a.n = n;
+    a.first = s->first;
+    a.last = s->last;
+    a.nslice = nslice;
+    a.cols = s->cols;
+    a.cnt = s->cf_cnt;
+    a.ptr = dev_ptr_out;
+    a.ecol = dev_ecol_out;
+    a.eval = dev_eval_out;
+    a.cap = cap_entries;
+    a.bad = s->fbad_dev;
+    HIPCHK(launch_fetch_compact(a, s->stream));
+    if (out_entries)  // ptr[n], behind the writing pass; read after the wait on the call's event below
+        HIPCHK(hipMemcpyAsync(s->cf_host, dev_ptr_out + n, 4, hipMemcpyDeviceToHost, s->stream));
+    const int rc = finish_device_fetch(s, dev_keys, (hipStream_t)stream);
+    if (!out_entries || rc == DML_E_HIP) return rc;
+    HIPCHK(hipEventSynchronize(s->fver.ev));
+    *out_entries = *s->cf_host;
+    if (rc) return rc;
+    if (*out_entries > cap_entries)
+        return set_err(DML_E_CAPACITY, "more entries than cap_entries: ptr is whole, no entry was written");
+    return DML_OK;
+}
+
 // Rows [lo, hi] (local indices), big-endian, row-major: DataOutputStream.write{Float,Int,Double}.
 static int write_rows_be(dml_store* s, int64_t lo, int64_t hi, uint8_t* out) {
     if (hi < lo) return DML_OK;

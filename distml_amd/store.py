@@ -399,6 +399,30 @@ class DataStore:
                                                              C.c_void_p(eval_ptr or None), rows.n,
                                                              C.c_void_p(stream or None)), self)
 
+    def handleFetchCompactRowsDevice(self, format: DataDesc, rows: DeviceKeys, ptr_ptr: int, ecol_ptr: Optional[int],
+                                     eval_ptr: Optional[int], cap_entries: int, stream: Optional[int] = None,
+                                     want_entries: bool = False) -> Optional[int]:
+        """The rows of a key list as a compact row list (dml_store_fetch_compact_rows_device), the
+        fetch counterpart of handlePushCompactRowsDevice: the int32[n + 1] at `ptr_ptr` gets the
+        entry ranges (list index j owns ptr[j] .. ptr[j+1]; `rows` is taken as it is, repeats and
+        any order included) and `ecol_ptr` / `eval_ptr` (room for `cap_entries` int32 each) the
+        non-zero counters of each row, columns ascending. ptr is always whole; when ptr[n] exceeds
+        `cap_entries` no entry is written (cap_entries 0 with None arrays only counts).
+        `want_entries`: the call waits for its own completion, returns ptr[n] and raises
+        NativeError(DML_E_CAPACITY) when that exceeded the capacity; otherwise it returns None and,
+        with a `stream`, never waits. IntMatrixStore only. `stream` and a key outside the shard
+        (an empty range, ArrayIndexOutOfBoundsException) as in handleFetchPlanesDevice."""
+        self._check_format(format)
+        if not isinstance(rows, DeviceKeys):
+            raise TypeError("handleFetchCompactRowsDevice takes DeviceKeys")
+        entries = C.c_int64()
+        check(_lib.load().dml_store_fetch_compact_rows_device(self._h, C.c_void_p(rows.ptr or None), rows.n,
+                                                              C.c_void_p(ptr_ptr or None), C.c_void_p(ecol_ptr or None),
+                                                              C.c_void_p(eval_ptr or None), int(cap_entries),
+                                                              C.byref(entries) if want_entries else None,
+                                                              C.c_void_p(stream or None)), self)
+        return entries.value if want_entries else None
+
     def writeAll(self, os=None) -> bytes:
         """Big-endian row-major dump (FloatMatrixStore.java:74-81); writes to `os` if given."""
         n = self._rows * self._cols * np.dtype(self.dtype).itemsize
@@ -688,6 +712,21 @@ def expand_fetch_device(format: DataDesc, cols: int, records_ptr: int, m: int, i
                                                 C.c_void_p(inverse_ptr or None), int(n),
                                                 C.c_void_p(values_ptr or None), C.c_void_p(alpha_ptr or None),
                                                 C.c_void_p(stream or None)))
+
+
+def expand_compact_rows_device(ptr_ptr: int, ecol_ptr: Optional[int], eval_ptr: Optional[int], m: int, entries: int,
+                               cols: int, inverse_ptr: Optional[int], n: int, plane_ptr: int,
+                               stream: Optional[int] = None) -> None:
+    """expand_fetch_device for a compact row list (handleFetchCompactRowsDevice's output): row j of
+    the int32[n][cols] at `plane_ptr` becomes the dense form of compact row `inverse[j]` of the `m`
+    rows (`ptr_ptr` int32[m + 1], `ecol_ptr` / `eval_ptr` int32[entries]); `inverse_ptr` None is
+    the identity (n == m). Repeated columns sum, a column outside [0, cols) adds nothing, and a
+    row whose inverse entry or entry range is out of bounds is left as it was. `stream` as in
+    unpack_fetch_device (dml_compact_rows_expand_device)."""
+    check(_lib.load().dml_compact_rows_expand_device(C.c_void_p(ptr_ptr or None), C.c_void_p(ecol_ptr or None),
+                                                     C.c_void_p(eval_ptr or None), int(m), int(entries), int(cols),
+                                                     C.c_void_p(inverse_ptr or None), int(n),
+                                                     C.c_void_p(plane_ptr or None), C.c_void_p(stream or None)))
 
 
 def compact_rows_split(keys: DeviceKeys, ptr_ptr: int, total_rows: int, world: int, row_off_ptr: int,

@@ -460,6 +460,53 @@ int dml_store_push_elems_device(dml_store* s, struct dml_coalescer* c, const int
 int dml_store_push_compact_rows_device(dml_store* s, const int64_t* dev_keys, const int32_t* dev_ptr,
                                        const int32_t* dev_ecol, const int32_t* dev_eval, int64_t m, void* stream);
 
+/* The rows of a key list as a compact row list: the owner's end of the compact FETCH, the
+ * counterpart of the call above (no JNI binding, for the same reason as the plane fetch). A
+ * requester on another rank gets 8 bytes per non-zero counter of its words instead of a dense
+ * 4 x cols-byte record per word (dml_fetch_compact.hip).
+ *
+ * dev_keys: int64[n] in device memory, 8-byte aligned, taken as it is: keys may repeat and come
+ * in any order, and row j of the output belongs to key j. The output is the compact row list of
+ * dml_coalesce_elems_compact_device without its key array (the caller holds the keys):
+ * dev_ptr_out int32[n + 1] with ptr[0] == 0, the entries of list index j at ptr[j] .. ptr[j+1] of
+ * dev_ecol_out / dev_eval_out. The entries are canonical: columns strictly ascending in
+ * [0, cols), eval the shard's counter, listed exactly when its 32 bits are non-zero (a negative
+ * counter left by read_all or sync_from is an entry). Every position is a sum of counts: no
+ * atomic decides one, and two calls on the same shard give equal bytes.
+ *
+ * Capacity: the entry count exists only on the device. ptr is always written whole, so ptr[n]
+ * is the count the list needs. When it exceeds cap_entries, NOTHING is stored into dev_ecol_out
+ * or dev_eval_out; otherwise exactly ptr[n] entries of each are. No kernel writes past
+ * cap_entries entries either way. With a non-null out_entries the call copies ptr[n] to the
+ * host behind the writing pass, waits for the call's completion (also with a non-null stream),
+ * stores it to *out_entries and returns DML_E_CAPACITY when it exceeded cap_entries. With
+ * out_entries == NULL and a non-null stream the call never waits: the caller reads ptr[n],
+ * which a transport needs anyway. cap_entries == 0 with null entry arrays is the count-only call.
+ *
+ * Served: IntMatrixStore with dense columns; every other store is DML_E_UNSUPPORTED, as is
+ * n x cols >= 2^31 (ptr is int32).
+ *
+ * Entry, ordering, `stream` and the key check are dml_store_fetch_planes_device's: every
+ * accepted push is retired and a deferred error returned; the kernels (a count pass, a scan,
+ * a writing pass that re-reads the rows) run on the store's apply stream behind every accepted
+ * push and before every later one, with no flush; a non-null `stream` waits for the event
+ * recorded behind them and the call returns at once, stream == NULL makes the call synchronous.
+ * Keys are compared as 64-bit values (first <= key <= last); a key outside the shard is never
+ * turned into an address and gets an empty entry range, every other row is as it should be, and
+ * the store's sticky error becomes DML_E_KEY_OUT_OF_SHARD with the key at the lowest such list
+ * index and col -1, returned by the call itself when stream == NULL and by the flush or the
+ * next read of the store otherwise.
+ *
+ * DML_E_INVALID_ARG, before anything is launched and with no state changed: a null s; n < 0 or
+ * n >= 2^31; cap_entries < 0; a null dev_keys or dev_ptr_out with n > 0; a null dev_ecol_out or
+ * dev_eval_out with cap_entries > 0; dev_keys not 8-byte aligned; an output not 4-byte aligned;
+ * an output that overlaps the keys or another output (ptr's n + 1 words, min(cap_entries,
+ * n x cols) entries). n == 0 returns DML_OK with nothing launched and nothing written on the
+ * device (*out_entries = 0). */
+int dml_store_fetch_compact_rows_device(dml_store* s, const int64_t* dev_keys, int64_t n, int32_t* dev_ptr_out,
+                                        int32_t* dev_ecol_out, int32_t* dev_eval_out, int64_t cap_entries,
+                                        int64_t* out_entries, void* stream);
+
 /* writeAll/readAll (FloatMatrixStore.java:74-91 etc.): big-endian row-major
  * values, the bytes DataOutputStream.writeFloat/writeInt/writeDouble emit.
  * read_all assigns the elements the stream holds before failing with
@@ -846,6 +893,31 @@ int dml_records_unpack_device(const dml_desc* desc, int32_t cols, uint32_t flags
 int dml_records_expand_device(const dml_desc* desc, int32_t cols, uint32_t flags, const void* dev_records,
                               int64_t m, const int32_t* dev_inverse, int64_t n, void* dev_values_out,
                               float* dev_alpha_out, void* stream);
+/* dml_compact_rows_expand_device is that expand for a compact row list: the requester's end of
+ * the compact fetch (dml_store_fetch_compact_rows_device). Row j of the
+ * int32[n][cols] plane dev_plane_out becomes the dense form of compact row dev_inverse[j] of the
+ * m rows (dev_ptr int32[m + 1], dev_ecol / dev_eval int32[entries]): zeros, plus the row's
+ * entries, so every byte of a written row is defined and the plane is what
+ * dml_store_fetch_planes_device of the occurrence list would have produced. A null dev_inverse
+ * is the identity and needs n == m. Store-less, on the caller's stream: stream == NULL waits,
+ * otherwise the kernel is enqueued and the inputs must be complete in `stream` order. The plane
+ * is written once (one kernel, no memset in front of a scatter).
+ *
+ * The list may come from another rank, so nothing of it is trusted. Entries need not be
+ * canonical: repeated columns sum mod 2^32, as the compact push sums them, in any order; an
+ * entry whose column lies outside [0, cols) adds nothing. A plane row is LEFT UNTOUCHED, as
+ * dml_records_expand_device leaves one, when its inverse entry lies outside [0, m) or its range
+ * is not 0 <= ptr[u] <= ptr[u + 1] <= entries; it is not reported. No word at or past `entries`
+ * of dev_ecol / dev_eval, past ptr[m] of dev_ptr or outside the n inverse words is ever read,
+ * and only the n x cols x 4 bytes of the plane are written.
+ *
+ * DML_E_INVALID_ARG, before any HIP call: m, n or entries negative; cols <= 0; m or n >= 2^31;
+ * a null dev_inverse with n != m; a pointer that is not 4-byte aligned; a null dev_plane_out
+ * with n > 0, dev_ptr with m > 0, dev_ecol or dev_eval with entries > 0; a plane that overlaps
+ * an input. n == 0, or m == 0 (no row can be named): DML_OK with nothing launched. */
+int dml_compact_rows_expand_device(const int32_t* dev_ptr, const int32_t* dev_ecol, const int32_t* dev_eval,
+                                   int64_t m, int64_t entries, int32_t cols, const int32_t* dev_inverse, int64_t n,
+                                   int32_t* dev_plane_out, void* stream);
 /* Output bytes of one wave instruction's 64 lines and of one block's tile in the codec's
  * kernels (k_rec_pack, k_rec_unpack, k_rec_expand): the sizes their tests place stream and plane ends at. */
 #define DML_CODEC_WAVE_BYTES 1024
