@@ -84,6 +84,7 @@ SIGNATURES = {
     "dml_store_push_planes_device": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "dml_store_push_elems_device": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "dml_store_push_compact_rows_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "dml_store_push_compact_rows_batch_device": (C.c_int, [_vp, _i32, _P(_vp), _P(_vp), _P(_vp), _P(_vp), _P(_i64), _vp]),
     "dml_store_fetch_compact_rows_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _P(_i64), _vp]),
     "dml_store_write_all": (C.c_int, [_vp, _vp, _i64, _P(_i64)]),
     "dml_store_read_all": (C.c_int, [_vp, _vp, _i64]),
@@ -229,6 +230,8 @@ DML_COALESCE_ELEMS_SLICE = 1024
 # key a block, and the most owners of dml_compact_rows_split
 DML_COMPACT_ROWS_LONG_ENTRIES = 1024
 DML_COMPACT_ROWS_MAX_WORLD = 1024
+# ... and the most runs of dml_store_push_compact_rows_batch_device (its run table is kernel arguments)
+DML_COMPACT_ROWS_BATCH_MAX_RUNS = 64
 
 
 class NativeLibraryMissing(RuntimeError):

@@ -395,6 +395,30 @@ struct PushCompactP {
 };
 // The check, the applies, their undo forms, then the verdict: all on `st`.
 hipError_t launch_push_compact(const PushCompactP& a, hipStream_t st);
+// ---- compact-row batch push (dml_compact_rows_batch.hip; dml_store_push_compact_rows_batch_device) ----
+// The non-empty runs of a batch, in list order, by value in the kernel arguments: off[q] is the
+// number of rows in front of run q (off[runs]: all of them, under 2^31). `cells` are the store's
+// kCrbCells words, all kNoPos between calls: a form cell and a bad cell per run, the stop word
+// (the runs that apply | (stop run + 1) << 8) and the lowest order word of a negative counter.
+constexpr int kCrbRuns = 64;  // DML_COMPACT_ROWS_BATCH_MAX_RUNS
+constexpr int kCrbForm = 0, kCrbBad = kCrbRuns, kCrbStop = 2 * kCrbRuns, kCrbOrd = kCrbStop + 1, kCrbCells = kCrbOrd + 1;
+struct CompactRun {
+    const int64_t* keys;
+    const int32_t* ptr;
+    const int32_t* ecol;
+    const int32_t* eval;
+};
+struct PushCompactBatchP {
+    CompactRun run[kCrbRuns];
+    uint32_t off[kCrbRuns + 1];
+    int32_t runs;
+    int32_t ncols;
+    int64_t nslice;
+    unsigned long long* cells;
+    ElemSink sink;  // `cell` and `bad` unused
+};
+// The check, the stop, the apply, its undo form, the verdict: all on `st`.
+hipError_t launch_push_compact_batch(const PushCompactBatchP& a, hipStream_t st);
 // dml_compact_rows_split's kernels: row_off / entry_off [world + 1] and the rebased ptr_out[m + world].
 hipError_t launch_compact_split(const int64_t* keys, int64_t m, const int32_t* ptr, int64_t total_rows, int32_t world,
                                 int64_t* row_off, int64_t* entry_off, int32_t* ptr_out, hipStream_t st);

@@ -843,6 +843,7 @@ void dml_store_destroy(dml_store* s) {
         (void)hipFree(s->fbad_dev);
         (void)hipFree(s->pe_cell);
         (void)hipFree(s->cr_scratch);
+        (void)hipFree(s->crb_cells);
         if (s->cr_handoff) (void)hipEventDestroy(s->cr_handoff);
         (void)hipFree(s->cf_cnt);
         if (s->cf_host) (void)hipHostFree(s->cf_host);

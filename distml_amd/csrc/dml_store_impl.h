@@ -178,6 +178,8 @@ struct dml_store {
     uint8_t* cr_scratch = nullptr;
     int64_t cr_cap = 0;
     hipEvent_t cr_handoff = nullptr;  // the caller's stream, where the apply stream takes over
+    // their batch form (dml_store_push_compact_rows_batch_device): the running call's kCrbCells words
+    unsigned long long* crb_cells = nullptr;
     // compact fetches (dml_store_fetch_compact_rows_device): the (key, slice) counts, cf_cap + 1
     // words grown on demand, and the pinned word a call that wants its entry count reads ptr[n] from
     uint32_t* cf_cnt = nullptr;

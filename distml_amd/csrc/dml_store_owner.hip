@@ -281,6 +281,73 @@ int dml_store_push_compact_rows_device(dml_store* s, const int64_t* dev_keys, co
     return collect_apply_check(s, true);
 }
 
+// The batch form (dml_compact_rows_batch.hip): the single call's entry, streams and
+// sticky verdicts. The non-empty runs go into the kernel arguments in list order (an empty run is a
+// single call that launches nothing), so nothing is uploaded and the host never waits.
+int dml_store_push_compact_rows_batch_device(dml_store* s, int32_t runs, const int64_t* const* dev_keys,
+                                             const int32_t* const* dev_ptr, const int32_t* const* dev_ecol,
+                                             const int32_t* const* dev_eval, const int64_t* m, void* stream) {
+    if (int rc = check_store(s)) return rc;
+    Entry in(s);
+    if (runs < 0 || runs > DML_COMPACT_ROWS_BATCH_MAX_RUNS)
+        return set_err(DML_E_INVALID_ARG, "runs outside 0 .. DML_COMPACT_ROWS_BATCH_MAX_RUNS");
+    if (runs > 0 && (!dev_keys || !dev_ptr || !dev_ecol || !dev_eval || !m))
+        return set_err(DML_E_INVALID_ARG, "null run table");
+    PushCompactBatchP a{};
+    int64_t total = 0;
+    for (int32_t q = 0; q < runs; ++q) {
+        if (m[q] < 0 || m[q] > 0x7FFFFFFFll) return set_err(DML_E_INVALID_ARG, "a run's row count outside 0 .. 2^31 - 1");
+        if (m[q] == 0) continue;
+        if (!dev_keys[q] || !dev_ptr[q] || !dev_ecol[q] || !dev_eval[q])
+            return set_err(DML_E_INVALID_ARG, "null keys, ptr, columns or values in a run with rows");
+        if (((uintptr_t)dev_keys[q] & 7) != 0) return set_err(DML_E_INVALID_ARG, "push keys are not 8-byte aligned");
+        if ((((uintptr_t)dev_ptr[q] | (uintptr_t)dev_ecol[q] | (uintptr_t)dev_eval[q]) & 3) != 0)
+            return set_err(DML_E_INVALID_ARG, "ptr, columns or values are not 4-byte aligned");
+        total += m[q];
+        if (total > 0x7FFFFFFFll) return set_err(DML_E_INVALID_ARG, "batches of 2^31 rows and more");
+        a.run[a.runs] = CompactRun{dev_keys[q], dev_ptr[q], dev_ecol[q], dev_eval[q]};
+        a.off[++a.runs] = (uint32_t)total;
+    }
+    if (vtype_of(s->desc) != kI32 || s->adagrad || !s->is_matrix)
+        return set_err(DML_E_UNSUPPORTED, "compact rows are IntMatrixStore updates: the record route serves the rest");
+    if (!s->desc.dense_column)
+        return set_err(DML_E_UNSUPPORTED, "sparse-column matrix rows are not supported (SURVEY defect 3)");
+    // a negative counter's order word: (run x rows + row) x cols + col, below kNoPos
+    if ((unsigned __int128)std::max(a.runs, 1) * (unsigned __int128)s->rows * (unsigned __int128)s->cols >= (unsigned __int128)kNoPos)
+        return set_err(DML_E_UNSUPPORTED, "runs x rows x cols does not fit 64 bits: make several calls");
+    if (int rc = retire_all(s)) return rc;
+    if (int rc = collect_apply_check(s, false)) return rc;
+    if (int rc = failed(s)) return rc;
+    if (a.runs == 0) return DML_OK;
+    if (!s->crb_cells) {
+        HIPCHK(hipMalloc((void**)&s->crb_cells, sizeof(unsigned long long) * kCrbCells));
+        HIPCHK(hipMemsetAsync(s->crb_cells, 0xFF, sizeof(unsigned long long) * kCrbCells, s->stream));  // all open
+    }
+    if (int rc = s->fver.ensure(s->stream)) return rc;
+    if (int rc = s->neg.ensure(s->stream)) return rc;
+    a.ncols = s->cols;
+    a.nslice = ((int64_t)s->cols + DML_COALESCE_ELEMS_SLICE - 1) / DML_COALESCE_ELEMS_SLICE;
+    a.cells = s->crb_cells;
+    a.sink.data = (int32_t*)s->data;
+    a.sink.first = s->first;
+    a.sink.last = s->last;
+    a.sink.cols = s->cols;
+    a.sink.neg = s->neg.dev;
+    a.sink.fver = s->fver.dev;
+    a.sink.apply = s->stream;
+    if (stream && (hipStream_t)stream != s->stream) {  // the runs are complete on `stream`: no host wait
+        if (!s->cr_handoff) HIPCHK(hipEventCreateWithFlags(&s->cr_handoff, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(s->cr_handoff, (hipStream_t)stream));
+        HIPCHK(hipStreamWaitEvent(s->stream, s->cr_handoff, 0));
+    }
+    HIPCHK(launch_push_compact_batch(a, s->stream));
+    if (int rc = s->fver.post(s->stream)) return rc;
+    if (int rc = s->neg.post(s->stream)) return rc;
+    if (stream) return DML_OK;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return collect_apply_check(s, true);
+}
+
 int dml_compact_rows_split(const int64_t* dev_keys, int64_t m, const int32_t* dev_ptr, int64_t total_rows,
                            int32_t world, int64_t* dev_row_off, int64_t* dev_entry_off, int32_t* dev_ptr_out,
                            void* stream) {

@@ -399,6 +399,27 @@ class DataStore:
                                                              C.c_void_p(eval_ptr or None), rows.n,
                                                              C.c_void_p(stream or None)), self)
 
+    def handlePushCompactRowsBatchDevice(self, format: DataDesc, runs, stream: Optional[int] = None) -> None:
+        """A batch of compact row lists in one pass over the shard
+        (dml_store_push_compact_rows_batch_device): `runs` is a sequence of at most
+        DML_COMPACT_ROWS_BATCH_MAX_RUNS tuples (rows, ptr_ptr, ecol_ptr, eval_ptr), each as
+        handlePushCompactRowsDevice takes them, one per source rank. The store ends byte for
+        byte, values and error state, where one handlePushCompactRowsDevice per run in list
+        order leaves it: every run's add is checked on its own, so the runs are not merged, but a
+        shard row that several runs list is read and written once and the batch is five launches.
+        A run of no rows may have None pointers. `stream`: the one stream on which every run is
+        complete, as in handlePushCompactRowsDevice."""
+        self._check_format(format)
+        runs = list(runs)
+        if not all(isinstance(r[0], DeviceKeys) for r in runs):
+            raise TypeError("handlePushCompactRowsBatchDevice takes DeviceKeys in every run")
+        n = len(runs)
+        cols = [(C.c_void_p * max(n, 1))(*(x or None for x in c)) for c in zip(*((r[0].ptr, *r[1:4]) for r in runs))] \
+            if n else [None] * 4
+        m = (C.c_int64 * max(n, 1))(*(int(r[0].n) for r in runs))
+        check(_lib.load().dml_store_push_compact_rows_batch_device(self._h, n, *cols, m if n else None,
+                                                                   C.c_void_p(stream or None)), self)
+
     def handleFetchCompactRowsDevice(self, format: DataDesc, rows: DeviceKeys, ptr_ptr: int, ecol_ptr: Optional[int],
                                      eval_ptr: Optional[int], cap_entries: int, stream: Optional[int] = None,
                                      want_entries: bool = False) -> Optional[int]:

@@ -460,6 +460,46 @@ int dml_store_push_elems_device(dml_store* s, struct dml_coalescer* c, const int
 int dml_store_push_compact_rows_device(dml_store* s, const int64_t* dev_keys, const int32_t* dev_ptr,
                                        const int32_t* dev_ecol, const int32_t* dev_eval, int64_t m, void* stream);
 
+/* `runs` compact row lists into an IntMatrixStore's shard in ONE pass: the owner's end of a group
+ * step, in which every source rank sends one run (no JNI binding, like the call above). The five
+ * arguments behind `runs` are HOST arrays of `runs` entries, read before the call returns, as
+ * dml_store_push_batch_device takes its pointers and lengths: (dev_keys[q], dev_ptr[q],
+ * dev_ecol[q], dev_eval[q], m[q]) is a compact row list exactly as the call above defines it,
+ * with its alignment rules; m[q] == 0 is allowed and that run's pointers may then be null.
+ *
+ * The store ends byte for byte (values, the sticky error triple, the closed state) where `runs`
+ * successive calls of dml_store_push_compact_rows_device, in list order on the same stream, leave
+ * it. The runs are NOT merged: every column of every listed row is checked after each run's add
+ * (IntMatrixStore.java:171-178), so a counter that run 0 drives negative and run 1 brings back
+ * closes the store at run 0. Per run: a malformed run applies nothing and closes the store
+ * (DML_E_INVALID_ARG, key or -1, col -1); a run whose smallest key lies below first applies
+ * nothing and one with a key above last applies its in-shard keys, both closing with
+ * DML_E_KEY_OUT_OF_SHARD unless a counter of the same run went negative; after the run that
+ * closes the store no later run applies anything. After the first negative counter at (run r,
+ * key, col) the shard holds every add of the runs before r and run r's adds up to and including
+ * that element in row-major order, and nothing behind it. A batch queued behind a closed,
+ * unreported verdict applies nothing. Entries need not be canonical and a row may have any
+ * number of them.
+ *
+ * A shard row that several runs list is read once and stored once, and the batch is five kernel
+ * launches whatever `runs` is (dml_compact_rows_batch.hip). The run table travels
+ * in the kernel arguments, hence DML_COMPACT_ROWS_BATCH_MAX_RUNS; a caller with more runs makes
+ * several calls, which compose by the rule above. Entry, `stream` (the one stream on which all
+ * runs are complete), ordering against later pushes and fetches with no flush, no host wait with
+ * a non-null stream, and stream == NULL making the call synchronous and returning its own error:
+ * all are the single call's.
+ *
+ * DML_E_INVALID_ARG, before anything is launched and with no state changed: a null s; runs < 0
+ * or runs > DML_COMPACT_ROWS_BATCH_MAX_RUNS; a null host array with runs > 0; an m[q] outside
+ * 0 .. 2^31 - 1; a null or misaligned device array with m[q] > 0; a total of m[q] of 2^31 and
+ * more. DML_E_UNSUPPORTED, at the same point: every store but IntMatrixStore with dense columns,
+ * and a shard of so many counters that runs x rows x cols does not fit 64 bits. runs == 0, or
+ * every run empty: DML_OK, nothing launched. */
+#define DML_COMPACT_ROWS_BATCH_MAX_RUNS 64
+int dml_store_push_compact_rows_batch_device(dml_store* s, int32_t runs, const int64_t* const* dev_keys,
+                                             const int32_t* const* dev_ptr, const int32_t* const* dev_ecol,
+                                             const int32_t* const* dev_eval, const int64_t* m, void* stream);
+
 /* The rows of a key list as a compact row list: the owner's end of the compact FETCH, the
  * counterpart of the call above (no JNI binding, for the same reason as the plane fetch). A
  * requester on another rank gets 8 bytes per non-zero counter of its words instead of a dense
